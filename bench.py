@@ -19,8 +19,14 @@ shard embarrassingly: every rank owns its own batches, there is no data-path col
 
 stdout carries ONE JSON line of <= 8 KB (`compact_line`): the headline (`value`: f16x3 mode, the library default --
 split-half operands, 22 bits, three f16 MFMAs per product, float32-grade results: tests/test_gpu_decisions_vs_oracle.py --
-frames resident in HBM, ONE resident batch re-used by every step: `config.resident_batch_reused`), the dominant kernel
-instance's `roofline`, `cpu_baseline`, and beside them
+frames resident in HBM, ONE resident batch re-used by every step: `config.resident_batch_reused`).  `value` and
+`ms_per_step` come from exactly the K = --steps timed steps that follow the --warmup steps.
+
+A plain run does only that: set up, warm up, time the K steps, write the last step's results if `--dump-outputs DIR` is
+given (`dump_outputs`: DIR/<name>.npy, float32 / float64, the same seeded inputs in every run) and print the line.
+`--full` measures everything else as well: the dominant kernel instance's `roofline`, `cpu_baseline`, `power`, and beside them
+  value_sustained               the headline workload over a region of >= --sustain-seconds (a 0.25 s region reads ~8 %
+                                above what the loop sustains -- the chip clocks to its power budget)
   value_f32 / roofline_f32      the same workload with every conv on the exact-f32 MFMA (the like-for-like arithmetic)
   value_f16x2                   the opt-in tolerance mode: the embedder alone on two of the three products (<= 5e-4 guarded at load)
   value_ingest                  the same workload fed from HOST memory: a raw rgb24 byte stream read into pinned buffers and
@@ -28,14 +34,12 @@ instance's `roofline`, `cpu_baseline`, and beside them
                                 batch, results gathered in order on rank 0 WHILE the region runs (a gather thread per rank) --
                                 the figure comparable with the reference's `.call`, whose first act is the host -> device
                                 copy of the batch (retinaface/wrapper.py:144)
-  value_k_steps                 the exact K = --steps region (`value` itself is quoted from a region of >= 2.5 s: a 0.25 s
-                                region reads ~8 % above what the loop sustains -- the chip clocks to its power budget)
   per_model                     BASELINE configs C2 (RetinaFace 32x640x640), C3 (ArcFace 256 crops), C4 (OpenPose
                                 16x368x656): images/s and roofline fraction each (N = 1 only)
-Everything else this run measured (every leg's full roofline object, power, per-rank host figures, per-model rows, the prose)
-goes to `gpurun_out/bench_detail.json` (`--detail PATH`) and to stderr; `--full` adds the legs of earlier rounds (bf16x3 / f16 /
-bf16 precisions, 1 and 4 faces per frame, pose weights without structured zeros); `--full-line` prints the detail object on
-stdout instead of the compact line (tools/*.sh).
+Everything else a --full run measured (every leg's full roofline object, power, per-rank host figures, per-model rows, the
+prose) goes to the detail file (`--detail PATH`) and to stderr; `--all-legs` (implies --full) adds the legs of earlier rounds
+(bf16x3 / f16 / bf16 precisions, 1 and 4 faces per frame, pose weights without structured zeros); `--full-line` prints the
+detail object on stdout instead of the compact line (tools/*.sh).
 `python bench.py --gpus N --single-process` (no torchrun) drives N devices from ONE process through
 terran_amd.pipeline.StreamPipeline (per device: lanes of upload / detect -> embed / pose threads) instead of one process
 per GPU; `--devices 0,0` puts two replicas on one card.
@@ -72,7 +76,7 @@ HBM_PEAK_GBPS = 8000.0
 # Beside it in the same line: `value_f16x2` (the opt-in tolerance mode: the embedder alone on two of the three products, guarded
 # at load time, arcface.calibrate_f16x2) and `value_f32` (every conv on the exact-f32 MFMA).
 HEADLINE = 'f16x3'
-SIDE_PRECISIONS = ('f32', 'f16x2')                                    # default side legs; --full: + bf16x3, f16, bf16
+SIDE_PRECISIONS = ('f32', 'f16x2')                                    # --full side legs; --all-legs: + bf16x3, f16, bf16
 # `dtype` of the compact line: <= 200 characters
 DTYPE_SHORT = {'f32': 'f32 (v_mfma_f32_32x32x2_f32)',
                'f16x3': 'f16x3: operands x = hi + lo (two IEEE halfs, 22 bits), 3 f16 MFMAs per product, f32 accumulate; float32-grade results',
@@ -230,7 +234,7 @@ class LoopStream(io.RawIOBase):
         return n
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=144)       # >= 2 s timed region at ~15 ms per step
@@ -241,16 +245,21 @@ def main():
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--precision', default=None, choices=['f32', 'f16x3', 'bf16x3', 'bf16', 'f16', 'f16x2'],
                     help='conv arithmetic mode of the headline number (default: $TERRAN_AMD_PRECISION or f16x3)')
-    ap.add_argument('--single-mode', action='store_true',
-                    help='headline measurement only (no f32 / faces-per-frame / sustained / ingest / per-model legs)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write the results of the last timed step (detections, embeddings, poses) as DIR/<name>.npy (dump_outputs)')
     ap.add_argument('--full', action='store_true',
-                    help='also the legs of earlier rounds: bf16x3 / f16 / bf16 precisions, 1 and 4 faces per frame, pose weights '
+                    help='measure everything beside the headline as well: sustained region, power, roofline profile step, ingest, '
+                         'other precisions, per-model rows, CPU baseline (off: only the K timed steps)')
+    ap.add_argument('--single-mode', action='store_true',
+                    help='with --full: headline measurement only (no f32 / faces-per-frame / ingest / per-model legs)')
+    ap.add_argument('--all-legs', action='store_true',
+                    help='implies --full; also the legs of earlier rounds: bf16x3 / f16 / bf16 precisions, 1 and 4 faces per frame, pose weights '
                          'without structured zeros, the embedder modes beside each other at C3 (detail file only)')
     ap.add_argument('--full-line', action='store_true', help='print the detail object on stdout instead of the compact line (tools)')
     ap.add_argument('--detail', default=os.path.join(REPO, 'gpurun_out', 'bench_detail.json'),
-                    help='where rank 0 writes everything the run measured (the stdout line is the <= 8 KB summary of it)')
+                    help='with --full: where rank 0 writes everything the run measured (the stdout line is the <= 8 KB summary of it)')
     ap.add_argument('--no-side-legs', action='store_true',
-                    help='headline + ingest legs only (no other precisions / faces per frame / random-weights / per-model legs): multi-rank rehearsals')
+                    help='with --full: headline + ingest legs only (no other precisions / faces per frame / random-weights / per-model legs): multi-rank rehearsals')
     ap.add_argument('--inflight', type=int, default=2, help='lanes per GPU: batches in flight, each on its own upload / detect / embed / pose streams '
                     '(2 / 3 / 4 measure alike to +4 % for 2 once the host threads block in their syncs, 1 is 4.5 % slower: profiles/r06_ab_inflight.txt, r06_energy_ab.txt)')
     ap.add_argument('--serial', action='store_true',
@@ -261,7 +270,7 @@ def main():
                     help='bounded run-ahead inside a pipeline: a task starts step i once all three finished step i - W (0 = unbounded)')
     ap.add_argument('--join-steps', action='store_true', help='join the face and pose threads after every step')
     ap.add_argument('--sustain-seconds', type=float, default=2.5,
-                    help='minimum length of the timed region `value` is quoted from (the K-step region is reported beside it)')
+                    help='with --full: minimum length of the region `value_sustained` is quoted from (`value` is the K-step region)')
     ap.add_argument('--side-seconds', type=float, default=1.5,
                     help='minimum length of the timed regions of the side legs (other precisions, faces per frame)')
     ap.add_argument('--lane-embedders', action='store_true',
@@ -273,8 +282,14 @@ def main():
     ap.add_argument('--single-process', action='store_true',
                     help='--gpus N devices driven by ONE process through the facades\' device-list fan-out')
     ap.add_argument('--devices', default=None, help='with --single-process: comma-separated device ids (repeats allowed)')
-    args = ap.parse_args()
-    args.side = not (args.single_mode or args.no_side_legs)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.all_legs
+    args.side = args.full and not (args.single_mode or args.no_side_legs)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
 
     os.environ.setdefault('GPU_MAX_HW_QUEUES', '12')     # before torch initialises HIP: see terran_amd/lib.py:load
     os.environ.setdefault('HIP_FORCE_DEV_KERNARG', '1')  # likewise (kernel arguments in device memory)
@@ -288,18 +303,70 @@ def main():
     finally:
         sys.stdout.flush()
     if result is not None:
+        outputs = result.pop('_outputs', None)          # (dets, feats, poses) of the last timed step
+        if args.dump_outputs:
+            dump_outputs(outputs, args.dump_outputs)
         detail = json.dumps(result)
-        try:
-            os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
-            with open(args.detail, 'w') as f:
-                f.write(detail + '\n')
-        except OSError as e:
-            print('bench: could not write %s: %s' % (args.detail, e), file=sys.stderr)
-        print(detail, file=sys.stderr)
-        sys.stderr.flush()
-        line = detail if (args.full_line or args.serial) else compact_line(result, os.path.relpath(args.detail, REPO))
+        if args.full:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.detail)), exist_ok=True)
+                with open(args.detail, 'w') as f:
+                    f.write(detail + '\n')
+            except OSError as e:
+                print('bench: could not write %s: %s' % (args.detail, e), file=sys.stderr)
+            print(detail, file=sys.stderr)
+            sys.stderr.flush()
+        line = detail if (args.full_line or args.serial) else compact_line(
+            result, os.path.relpath(args.detail, REPO) if args.full else None)
         os.write(real_stdout, (line + '\n').encode())
     os.close(real_stdout)
+
+
+DUMP_LIMIT = 60 << 20      # bytes of array data --dump-outputs may write (under 64 MB with the .npy headers)
+
+
+def step_arrays(dets, feats, poses):
+    """One step's results as flat float arrays, one row per detection / embedded face / person, in frame order; the
+    `*_counts` arrays say how many rows each frame owns.  Integer fields are stored as float64 (exact)."""
+    def rows(per_frame, key, tail):
+        return np.array([x[key] for d in per_frame for x in d], np.float64).reshape((-1,) + tail)
+    emb = [np.asarray(f, np.float32).reshape(len(f), -1) for f in feats]
+    return {
+        'det_counts': np.array([len(d) for d in dets], np.float64),
+        'det_bbox': rows(dets, 'bbox', (4,)),
+        'det_landmarks': rows(dets, 'landmarks', (5, 2)),
+        'det_score': rows(dets, 'score', ()),
+        'emb_counts': np.array([len(f) for f in emb], np.float64),
+        'embeddings': np.concatenate(emb) if any(len(f) for f in emb) else np.zeros((0, 512), np.float32),
+        'pose_counts': np.array([len(p) for p in poses], np.float64),
+        'pose_keypoints': rows(poses, 'keypoints', (18, 3)),
+        'pose_score': rows(poses, 'score', ()),
+    }
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT):
+    """--dump-outputs: what the timed path returned for its last step, as out_dir/<name>.npy (step_arrays).  Should the
+    arrays outgrow `limit`, a fixed seeded sample of whole frames is kept; `frame_index` names the frames written."""
+    dets, feats, poses = outputs
+    n = len(dets)
+    keep = np.arange(n)
+    arrays = step_arrays(dets, feats, poses)
+    if sum(a.nbytes for a in arrays.values()) > limit:
+        per_frame = [step_arrays([d], [f], [p]) for d, f, p in zip(dets, feats, poses)]
+        size = [sum(a.nbytes for a in pf.values()) + 8 for pf in per_frame]
+        chosen, total = [], 0
+        for i in np.random.default_rng(0).permutation(n):
+            if total + size[i] <= limit:
+                chosen.append(i)
+                total += size[i]
+        keep = np.sort(np.array(chosen, np.int64))
+        arrays = step_arrays([dets[i] for i in keep], [feats[i] for i in keep], [poses[i] for i in keep])
+    arrays['frame_index'] = keep.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    return sorted(arrays)
 
 
 LINE_LIMIT = 8192          # the driver keeps the last 8 KB of stdout: the line must fit (tests/test_host_cpu.py::test_bench_line_is_compact)
@@ -340,7 +407,7 @@ def compact_line(result, detail_path=None):
     if isinstance(cb, dict):
         line['cpu_baseline'] = {k: (v[:160] if isinstance(v, str) else v) for k, v in cb.items()
                                 if k in ('value', 'unit', 'cores', 'kind', 'sample', 'error')}
-    for k in ('value_k_steps', 'value_f32', 'value_f16x3', 'value_f16x2', 'value_ingest'):
+    for k in ('value_sustained', 'value_f32', 'value_f16x3', 'value_f16x2', 'value_ingest'):
         if r.get(k) is not None:
             line[k] = r[k]
     if isinstance(r.get('roofline_f32'), dict):
@@ -399,17 +466,17 @@ def run(args):
                      % (args.gpus, args.gpus))
         args.gpus = world
 
-    import torch
     dist = None
     gather_group = None
     # RCCL (backend "nccl") on the GPU box; TA_BENCH_BACKEND=gloo lets the multi-rank path be exercised on a
     # single-GPU box (ranks then share device LOCAL_RANK % device_count).
     backend = os.environ.get('TA_BENCH_BACKEND', 'nccl')
-    n_dev = max(torch.cuda.device_count(), 1)
-    device_index = local_rank % n_dev
     use_dist = world > 1 or bool(os.environ.get('TA_BENCH_FORCE_DIST'))     # FORCE: exercise the RCCL calls at N=1
-    if use_dist:
+    device_index = local_rank
+    if use_dist:                                  # torch only for the collectives: a single-rank run never imports it
+        import torch
         import torch.distributed as dist
+        device_index = local_rank % max(torch.cuda.device_count(), 1)
         if backend == 'nccl':
             torch.cuda.set_device(device_index)
             dist.init_process_group(backend='nccl', rank=rank, world_size=world,
@@ -426,7 +493,7 @@ def run(args):
     # this rank's host threads (task threads, reader threads, the pinned staging they touch first) on the cores of the socket
     # its GPU hangs off: at 2 600 frames/s a rank moves 16 GB/s through pinned memory (terran_amd/affinity.py)
     placement = affinity.bind(device_index)
-    power_hw = telemetry.hwmon_of_pci(placement.get('pci'))
+    power_hw = telemetry.hwmon_of_pci(placement.get('pci')) if args.full else None
 
     # Host side: a pipeline of three host threads per GPU, each with its own context (HIP stream + scratch):
     # detection, embedding (fed the detections of its batch through a queue) and pose.  Kernels of the streams
@@ -598,7 +665,8 @@ def run(args):
     # a-time modes (--serial / --join-steps) and for the event-profiled serial step the roofline figures come from.
     from terran_amd.pipeline import StreamPipeline
     streaming = not (args.serial or args.join_steps)
-    pipes = [Pipeline(True)]
+    # a plain streaming run times the engine alone: no second set of models for the profiled serial step
+    pipes = [Pipeline(True)] if (args.full or not streaming) else []
     engine = {}
 
     def sync():
@@ -693,16 +761,26 @@ def run(args):
             engine['resident'] = engine['sp'].scatter(work['frames'])            # resident in HBM before timing
         if args.warmup:
             run_steps(args.warmup if not streaming else max(args.warmup, 2 * L))      # every lane warms its plans
-        sampler = telemetry.PowerSampler(power_hw, bdf=placement.get('pci')).start()   # this rank's GPU: socket power / shader clock (sysfs), energy / throttlers (SMI)
+        sampler = telemetry.PowerSampler(power_hw, bdf=placement.get('pci')).start() if args.full else None   # this rank's GPU: socket power / shader clock (sysfs), energy / throttlers (SMI)
         cpu0 = time.process_time()
         elapsed, out = timed(steps)
-        res = {'elapsed_k': elapsed, 'steps_k': steps, 'elapsed': elapsed, 'steps': steps, 'out': out}
+        res = {'elapsed_k': elapsed, 'steps_k': steps, 'out_k': out, 'elapsed': elapsed, 'steps': steps, 'out': out}
         # host side of this rank over the K-step region: CPU-seconds of the whole process (all lanes' threads) per step, live threads
         res['host'] = {'cpu_s_per_step': round((time.process_time() - cpu0) / steps, 5), 'threads': threading.active_count()}
+        if not args.full:                                # a plain run: the K timed steps are all it measures
+            if streaming:
+                for fr in engine['resident']:
+                    fr.free()
+                n_l, n_c = engine['sp'].embed_stats()
+                res['crops_per_embed_launch'] = n_c / n_l if n_l else 0.0
+                engine.pop('sp').close()
+            for p in pipes:
+                p.unload()
+            return res
         # The chip clocks to its power budget: a region of a few tenths of a second reads ~8 % above what the same loop
-        # sustains.  Every figure of the line therefore comes from a region of >= `min_seconds`; the exact-K region the
-        # driver asked for is reported beside it (`value_k_steps`).  The step count follows from the max-over-ranks time of
-        # the K-step region, so it is the same on every rank.
+        # sustains.  The side figures of a --full line therefore come from a region of >= `min_seconds` (`value_sustained`
+        # for the headline); `value` stays the exact-K region the driver asked for.  The step count follows from the
+        # max-over-ranks time of the K-step region, so it is the same on every rank.
         if min_seconds > 0 and elapsed < min_seconds and not (args.serial or args.join_steps):
             k = int(np.ceil(min_seconds / (elapsed / steps)))
             sampler.stop()
@@ -862,7 +940,7 @@ def run(args):
     #    with their power objects; if they differ by more than 2 % the un-zeroed one IS the headline (`value`).
     legs = {'decoder_pose_weights': head}
     headline_leg = 'decoder_pose_weights'
-    if (args.side and args.full and not (args.serial or args.join_steps)) or os.environ.get('TA_BENCH_RANDOM_LEG'):
+    if args.full and ((args.side and args.all_legs and not (args.serial or args.join_steps)) or os.environ.get('TA_BENCH_RANDOM_LEG')):
         from terran_amd import synth, weights
         work.update(sd_p=weights.make_openpose_state(), frames=synth.frames(900 + rank, args.batch, H, W))
         try:
@@ -876,7 +954,7 @@ def run(args):
                 if k_ in head:
                     legs['random_pose_weights'][k_] = head[k_]
             head = legs['random_pose_weights']
-    elapsed, steps_timed, out, klass = head['elapsed'], head['steps'], head['out'], head['klass']
+    elapsed, steps_timed, out, klass = head['elapsed'], head['steps'], head['out'], head.get('klass')
 
     def drift(res):
         """Discrete results of a leg's last step against the exact-f32 leg's on the same frames: detections (rounded boxes, as sets per
@@ -900,7 +978,7 @@ def run(args):
     others = {}
     primary_drift = None
     if args.side:
-        for prec in (('f32', 'f16x3', 'bf16x3', 'f16', 'f16x2', 'bf16') if args.full else SIDE_PRECISIONS):
+        for prec in (('f32', 'f16x3', 'bf16x3', 'f16', 'f16x2', 'bf16') if args.all_legs else SIDE_PRECISIONS):
             if prec != primary:
                 r2 = run_mode(prec, max(L, args.steps // 2), min_seconds=args.side_seconds)
                 others[prec] = {'value': fps(r2['elapsed'], r2['steps']), 'steps': r2['steps'],
@@ -918,7 +996,7 @@ def run(args):
 
     # SURVEY.md 8(d) quotes the workload at F = 1 and F = 4 faces per frame: same pipeline, headline precision
     other_faces = {}
-    if args.side and args.full:
+    if args.side and args.all_legs:
         for nf in (1, 4):
             if nf != F:
                 face_state['F'] = nf
@@ -973,21 +1051,18 @@ def run(args):
         dets, feats, poses = out
         result = {
             'metric': 'frames/sec 1080p detect+embed+pose',
-            # `value`, `ms_per_step`, `timed_region_s`: the region of >= --sustain-seconds (`timed_steps` steps, barrier + sync on
-            # both sides, max over ranks); the EXACT K = `steps` region the caller asked for, timed the same way right before
-            # it, is `value_k_steps` / `ms_per_step_k_steps` / `timed_region_s_k_steps` (a 0.25 s region reads ~8 % high: the
-            # chip has not settled on its sustained clock yet)
-            'value': fps(elapsed, steps_timed),
+            # `value`, `ms_per_step`, `timed_region_s`: the EXACT K = `steps` region the caller asked for (barrier + sync on both
+            # sides, max over ranks).  With --full the region of >= --sustain-seconds timed right after it is `value_sustained` /
+            # `ms_per_step_sustained` / `timed_region_s_sustained` (a 0.25 s region reads ~8 % high: the chip has not settled on its
+            # sustained clock yet)
+            'value': fps(head['elapsed_k'], head['steps_k']),
             'unit': 'frames/s',
             'n_gpus': world,
             'steps': args.steps,
             'warmup': args.warmup,
-            'ms_per_step': round(elapsed / steps_timed * 1e3, 3),
-            'timed_region_s': round(elapsed, 3),
-            'timed_steps': steps_timed,
-            'value_k_steps': fps(head['elapsed_k'], head['steps_k']),
-            'ms_per_step_k_steps': round(head['elapsed_k'] / head['steps_k'] * 1e3, 3),
-            'timed_region_s_k_steps': round(head['elapsed_k'], 3),
+            'ms_per_step': round(head['elapsed_k'] / head['steps_k'] * 1e3, 3),
+            'timed_region_s': round(head['elapsed_k'], 3),
+            'timed_steps': head['steps_k'],
             'higher_is_better': True,
             'scaling': 'weak',
             'vs_baseline': None,
@@ -1012,8 +1087,6 @@ def run(args):
                 'faces_per_frame': F,
                 'detections_per_frame': round(float(np.mean([len(d) for d in dets])), 1),
                 'humans_per_frame': round(float(np.mean([len(p) for p in poses])), 2),
-                'pose_peaks_per_frame': round(pipes[0].ctxs[2].pose_stats()[0] / float(args.batch), 1),
-                'pose_limb_connections_per_frame': round(pipes[0].ctxs[2].pose_stats()[1] / float(args.batch), 1),
                 'sharding': 'frames split over ranks, no data-path collective',
                 'host_placement_per_rank': placements,
                 # per rank: CPU-seconds the whole process (every lane's threads) burned per step of the timed region, its live threads and
@@ -1032,17 +1105,29 @@ def run(args):
                                    'batches at once (>= %d crops or %.0f ms; %.0f crops per launch measured)'
                                    % (args.embed_min_crops, args.embed_max_wait * 1e3, head.get('crops_per_embed_launch', 0))),
             },
+            # the results of the last of the K timed steps (--dump-outputs), taken off the object before it is printed
+            '_outputs': head['out_k'],
+        }
+        if pipes:
+            result['config']['pose_peaks_per_frame'] = round(pipes[0].ctxs[2].pose_stats()[0] / float(args.batch), 1)
+            result['config']['pose_limb_connections_per_frame'] = round(pipes[0].ctxs[2].pose_stats()[1] / float(args.batch), 1)
+    if rank == 0 and args.full:
+        result.update({
+            'value_sustained': fps(elapsed, steps_timed),
+            'ms_per_step_sustained': round(elapsed / steps_timed * 1e3, 3),
+            'timed_region_s_sustained': round(elapsed, 3),
+            'timed_steps_sustained': steps_timed,
             # `roofline` = the DOMINANT kernel instance (most HIP-event time in one serial step of this process): algorithmic FLOPs per
             # launch over its average launch duration.  `roofline.all_conv_kernels` = every implicit-GEMM launch of the step together
-            # (serial, and over the pipelined step `value` is made of -- above the serial figure because concurrent streams fill the
-            # CUs one kernel's tail and launch gaps leave idle).
+            # (serial, and over the pipelined step `value_sustained` is made of -- above the serial figure because concurrent streams
+            # fill the CUs one kernel's tail and launch gaps leave idle).
             'roofline': roofline_object(primary, klass, elapsed / steps_timed),
             'stage_ms_per_step': {k: v['ms'] for k, v in klass.items() if k != 'instances'},
             # algorithmic bytes / kernel time of the HBM-bound kernel classes (peak 8000 GB/s); post-processing
             # mixes the pose-map stream with latency-bound selection / grouping kernels
             'stage_hbm_gbps': {k: round(v['work'] / (v['ms'] * 1e-3) / 1e9, 1) for k, v in klass.items()
                                if k not in ('conv_igemm', 'instances') and v['ms'] > 0},
-        }
+        })
         if args.serial:
             # --serial is the mode the rocprofv3 kernel statistics under profiles/ are taken in: the algorithmic FLOPs every
             # dense-conv kernel INSTANCE did over this whole run (warm-up, timed and event-profiled steps), so that the
@@ -1078,7 +1163,7 @@ def run(args):
             result['value_f16_embedder'] = others['f16']['value']
             result['ms_per_step_f16_embedder'] = others['f16']['ms_per_step']
             result['roofline_f16_embedder'] = others['f16']['roofline']
-        # rank 0's GPU over the region `value` comes from, driver-run: amdgpu hwmon power1_* / freq1_input every 50 ms.  In
+        # rank 0's GPU over the region `value_sustained` comes from, driver-run: amdgpu hwmon power1_* / freq1_input every 50 ms.  In
         # f16x3 the chip sits at its package power cap with the shader clock ~20 % under the 2.4 GHz the peak is quoted at
         # (DESIGN.md section 4); null when the box exposes no sensors
         if head.get('power') and head['power'].get('sclk_mhz_mean') and result['roofline'].get('all_conv_kernels'):
@@ -1104,12 +1189,12 @@ def run(args):
     if rank == 0 and world == 1 and args.side:
         try:
             result['per_model'] = per_model(runtime.get_context(device_index), [primary, 'f32'] if primary != 'f32' else ['f32'],
-                                            embedder_modes=args.full)
+                                            embedder_modes=args.all_legs)
         except Exception as ex:
             import traceback
             traceback.print_exc()
             result['per_model'] = {'error': '%s: %s' % (type(ex).__name__, ex)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             result['cpu_baseline'] = cpu_baseline(frames_host[:args.cpu_frames], F, sd_r, sd_a, sd_p, fallback_lm)
         except Exception as ex:
@@ -1294,6 +1379,25 @@ def run_single_process(args):
     warm = max(args.warmup, 2 * L)
     timed((resident for _ in range(warm)), warm)
     elapsed, out = timed((resident for _ in range(args.steps)), args.steps)
+    per_step = elapsed / args.steps
+    result = {
+        'metric': 'frames/sec 1080p detect+embed+pose', 'value': round(len(frames_host) * args.steps / elapsed, 3),
+        'unit': 'frames/s', 'n_gpus': len(set(devices)), 'steps': args.steps, 'warmup': warm,
+        'ms_per_step': round(per_step * 1e3, 3), 'timed_region_s': round(elapsed, 3), 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': DTYPES[prec], 'data': 'synthetic',
+        'config': {'workload': 'BASELINE configs[4], ONE process: %d device replica(s) %s x %d lanes of upload / detect -> embed / pose '
+                               'threads (terran_amd.pipeline.StreamPipeline), %d frames per replica per step, shards resident in HBM, '
+                               'results gathered in frame order on the calling thread' % (n, devices, L, args.batch),
+                   'precision': prec, 'frames_per_step': len(frames_host), 'faces_per_frame': F,
+                   'detections_per_frame': round(float(np.mean([len(d) for d in out[0]])), 1),
+                   'humans_per_frame': round(float(np.mean([len(p) for p in out[2]])), 2)},
+        '_outputs': out}
+    if not args.full:                                              # a plain run: the K timed steps are all it measures
+        for fr in resident:
+            if fr is not None:
+                fr.free()
+        pipe.close()
+        return result
     # one batch alone with a HIP event pair around every launch of lane 0 of device 0 -> the per-class times of a step
     lane = pipe.lanes[0][0]
     ctxs = [lane.det.model.ctx, lane.est.model.ctx] + ([lane.rec.model.ctx] if lane.rec is not None else
@@ -1318,29 +1422,19 @@ def run_single_process(args):
         if fr is not None:
             fr.free()
     pipe.close()
-    per_step = elapsed / args.steps
     roof = conv_roofline(prec, klass['conv_igemm'])
     work_step = klass['conv_igemm']['work'] * n                    # every device does one device-0 share per step
     roof['pipelined_achieved'] = round(work_step / per_step / 1e12, 2)
     roof['pipelined_frac'] = round(work_step / per_step / 1e12 / (PEAKS[prec][0] * len(set(devices))), 4)
-    return {
-        'metric': 'frames/sec 1080p detect+embed+pose', 'value': round(len(frames_host) * args.steps / elapsed, 3),
-        'unit': 'frames/s', 'n_gpus': len(set(devices)), 'steps': args.steps, 'warmup': warm,
-        'ms_per_step': round(per_step * 1e3, 3), 'timed_region_s': round(elapsed, 3), 'higher_is_better': True, 'scaling': 'weak',
-        'vs_baseline': None, 'dtype': DTYPES[prec], 'data': 'synthetic',
-        'config': {'workload': 'BASELINE configs[4], ONE process: %d device replica(s) %s x %d lanes of upload / detect -> embed / pose '
-                               'threads (terran_amd.pipeline.StreamPipeline), %d frames per replica per step, shards resident in HBM, '
-                               'results gathered in frame order on the calling thread' % (n, devices, L, args.batch),
-                   'precision': prec, 'frames_per_step': len(frames_host), 'faces_per_frame': F,
-                   'detections_per_frame': round(float(np.mean([len(d) for d in out[0]])), 1),
-                   'humans_per_frame': round(float(np.mean([len(p) for p in out[2]])), 2)},
+    result.update({
         'roofline': roof,
         'stage_ms_per_step': {k_: v['ms'] for k_, v in klass.items()},
         'ingest': {'value': round(len(frames_host) * k_in / e_in, 3), 'unit': 'frames/s', 'steps': k_in,
                    'ms_per_step': round(e_in / k_in * 1e3, 3), 'host_to_device_mb_per_step': round(frames_host.nbytes / 1e6, 1),
                    'what': 'the same loop fed from host memory: every batch is cut into contiguous shards, each uploaded by its '
                            "lane's upload thread on its own stream (scatter), results gathered in order (gather), all inside the timed region"},
-        'value_ingest': round(len(frames_host) * k_in / e_in, 3)}
+        'value_ingest': round(len(frames_host) * k_in / e_in, 3)})
+    return result
 
 
 def cpu_baseline(frames_host, F, sd_r, sd_a, sd_p, fallback_lm):

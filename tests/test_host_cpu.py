@@ -822,6 +822,77 @@ def test_bench_line_is_compact():
     assert len(bench.compact_line(detail)) < 8192
 
 
+def test_bench_side_legs_need_full():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline alone; every side leg needs --full (--all-legs
+    implies it), and --dump-outputs is there in both modes."""
+    import bench
+    a = bench.parse_args(['--gpus', '1', '--steps', '7', '--warmup', '2'])
+    assert (a.steps, a.warmup, a.full, a.side, a.all_legs, a.dump_outputs) == (7, 2, False, False, False, None)
+    a = bench.parse_args(['--full'])
+    assert a.full and a.side and not a.all_legs
+    assert not bench.parse_args(['--full', '--single-mode']).side
+    a = bench.parse_args(['--all-legs', '--dump-outputs', 'd'])
+    assert a.full and a.side and a.dump_outputs == 'd'
+
+
+def test_bench_plain_line():
+    """The line of a plain run (no roofline, power or side legs in the result) carries the contract's keys and no detail path."""
+    import json
+    import bench
+    result = {'metric': 'frames/sec 1080p detect+embed+pose', 'value': 2200.5, 'unit': 'frames/s', 'n_gpus': 1, 'steps': 40, 'warmup': 5,
+              'ms_per_step': 14.542, 'timed_region_s': 0.582, 'timed_steps': 40, 'higher_is_better': True, 'scaling': 'weak',
+              'vs_baseline': None, 'dtype': bench.DTYPES['f16x3'], 'data': 'synthetic',
+              'config': {'precision': 'f16x3', 'frames_per_gpu_step': 32, 'faces_per_frame': 2}}
+    d = json.loads(bench.compact_line(result))
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step', 'steps', 'warmup', 'timed_steps'):
+        assert d[k] == (bench.DTYPE_SHORT['f16x3'] if k == 'dtype' else result[k]), k
+    assert 'detail' not in d and d['roofline'] is None
+
+
+def _step_results(seed, n_frames, dets_per_frame=(0, 3), people_per_frame=(0, 2), faces=2):
+    rng = np.random.default_rng(seed)
+    dets, feats, poses = [], [], []
+    for _ in range(n_frames):
+        nd = int(rng.integers(*dets_per_frame, endpoint=True))
+        dets.append([{'bbox': rng.integers(0, 1000, 4).astype(np.int32), 'landmarks': rng.integers(0, 1000, (5, 2)).astype(np.int32),
+                      'score': np.float32(rng.random())} for _ in range(nd)])
+        feats.append(rng.standard_normal((faces, 512)).astype(np.float32))
+        npp = int(rng.integers(*people_per_frame, endpoint=True))
+        poses.append([{'keypoints': rng.integers(0, 500, (18, 3)).astype(np.int32), 'score': float(rng.random())} for _ in range(npp)])
+    return dets, feats, poses
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: every array of the last step as float32 / float64 .npy, rows in frame order with per-frame counts; past
+    the size limit a fixed seeded sample of whole frames, the same one every run."""
+    import bench
+    dets, feats, poses = _step_results(3, 6)
+    names = bench.dump_outputs((dets, feats, poses), str(tmp_path / 'all'))
+    got = {n: np.load(str(tmp_path / 'all' / (n + '.npy'))) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got['det_counts'].tolist() == [len(d) for d in dets] and got['frame_index'].tolist() == list(range(6))
+    assert np.array_equal(got['det_bbox'], np.array([x['bbox'] for d in dets for x in d]).reshape(-1, 4))
+    assert np.array_equal(got['det_landmarks'], np.array([x['landmarks'] for d in dets for x in d]).reshape(-1, 5, 2))
+    assert np.array_equal(got['det_score'], [float(x['score']) for d in dets for x in d])
+    assert got['embeddings'].dtype == np.float32 and np.array_equal(got['embeddings'], np.concatenate(feats))
+    assert np.array_equal(got['pose_keypoints'], np.array([x['keypoints'] for p in poses for x in p]).reshape(-1, 18, 3))
+    assert got['pose_counts'].tolist() == [len(p) for p in poses]
+    # a limit below the whole step: a subset of frames, the same on every call, within the limit
+    dets, feats, poses = _step_results(4, 40, dets_per_frame=(5, 5), people_per_frame=(1, 1))
+    limit = 12 * 5000
+    picked = []
+    for run in ('a', 'b'):
+        names = bench.dump_outputs((dets, feats, poses), str(tmp_path / run), limit=limit)
+        arrays = {n: np.load(str(tmp_path / run / (n + '.npy'))) for n in names}
+        assert 0 < len(arrays['frame_index']) < 40 and sum(a.nbytes for a in arrays.values()) <= limit
+        keep = arrays['frame_index'].astype(int)
+        assert np.array_equal(arrays['embeddings'], np.concatenate([feats[i] for i in keep]))
+        picked.append(keep.tolist())
+    assert picked[0] == picked[1]
+    # the default limit keeps the whole output under 64 MB
+    assert bench.DUMP_LIMIT + 4096 < 64e6
+
+
 def test_smi_counter_deltas():
     """telemetry.SmiCounters.delta: joules, mean power and per-throttler residency (% of the region) from two readings of the SMI
     accumulators; missing fields stay absent, a wrapped energy counter yields no energy figure."""

@@ -10,10 +10,10 @@ for i in $(seq $R); do
     for w in $cfg; do
       if [[ ${#args[@]} -eq 0 && "$w" == *=* && "$w" != --* ]]; then envs+=("$w"); else args+=("$w"); fi
     done
-    env "${envs[@]}" python bench.py --single-mode --no-cpu-baseline --steps 120 --warmup 8 --detail /tmp/ab_detail.json ${4:-} "${args[@]}" 2>/dev/null | python -c "
+    env "${envs[@]}" python bench.py --full --single-mode --no-cpu-baseline --steps 120 --warmup 8 --detail /tmp/ab_detail.json ${4:-} "${args[@]}" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read())
 p=d.get('power') or {}
-print('%-44s | %8.1f frames/s  k-steps %8.1f | %s W %s MHz | %s J/frame | ppt %s %% | host %s cpu-s/step' % ('$cfg', d['value'], d['value_k_steps'], p.get('power_w_mean'), p.get('sclk_mhz_mean'), p.get('energy_j_per_frame'), (p.get('throttle') or {}).get('ppt'), d['config'].get('host_cpu_s_per_step')))"
+print('%-44s | %8.1f frames/s  k-steps %8.1f | %s W %s MHz | %s J/frame | ppt %s %% | host %s cpu-s/step' % ('$cfg', d['value_sustained'], d['value'], p.get('power_w_mean'), p.get('sclk_mhz_mean'), p.get('energy_j_per_frame'), (p.get('throttle') or {}).get('ppt'), d['config'].get('host_cpu_s_per_step')))"
   done
 done
