@@ -97,6 +97,31 @@ int ta_frames_resize_bicubic(ta_ctx* ctx, const ta_frames* src, int dst_h, int d
 int ta_frames_paste(ta_ctx* ctx, const ta_frames* src, int src_index, ta_frames* dst, int dst_index,
                     int top, int left);
 
+/* ---- drawing (terran/vis/pillow.py: vis_faces / vis_poses) ----------------------------- */
+/* Draws an ordered list of primitives into `frames` in place, Pillow's ImageDraw.Draw(img, 'RGBA') semantics bit for bit:
+ * ink blended as DIV255(in * (255 - a) + ink * a), each pixel once per primitive, everything clipped to the frame.  Where
+ * primitives of one frame overlap, a pixel sees them in list order; primitives of different frames may be interleaved.
+ *   TA_DRAW_BAR   filled axis-aligned rectangle, pixels x0..x1 x y0..y1 inclusive (x1 >= x0, y1 >= y0).  A rectangle
+ *                 outline of alpha 255 (draw.rectangle(outline=, width=)) is a set of bars.
+ *   TA_DRAW_LINE  draw.line([x0, y0, x1, y1], width=width): width <= 1 is the thin Bresenham line (both end points
+ *                 drawn), a wider one the quadrilateral Pillow builds around the segment (coincident end points: one pixel).
+ *   TA_DRAW_DISC  draw.ellipse([x0, y0, x1, y1], fill=): the filled ellipse in that box (x1 >= x0, y1 >= y0; the
+ *                 box's width and height at most 32768).
+ * Coordinates are pixels (what Pillow's int() of the float coordinates gives), |coordinate| <= 2^24.  The call runs on
+ * `ctx`'s stream (a batch of another context on the same device may be drawn into) and returns when the drawing is done.
+ * TA_E_INVALID: frame index out of range, unknown kind, inverted box, negative width, coordinate out of range. */
+#define TA_DRAW_BAR 0
+#define TA_DRAW_LINE 1
+#define TA_DRAW_DISC 2
+typedef struct ta_draw_prim {
+  int32_t frame;       /* image index in the batch                  */
+  int32_t kind;        /* TA_DRAW_*                                 */
+  int32_t x0, y0, x1, y1;
+  int32_t width;       /* TA_DRAW_LINE only                         */
+  uint8_t rgba[4];     /* ink and alpha                             */
+} ta_draw_prim;
+int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n);
+
 /* ---- models ---------------------------------------------------------------------------- */
 /* `blob` is the packed model produced by terran_amd/pack.py from a Terran state_dict
  * (replaces load_model(): retinaface/wrapper.py:16-22, arcface/wrapper.py:13-19,

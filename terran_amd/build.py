@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libterran_amd.so')
 SOURCES = ['runtime.hip', 'conv_igemm.hip', 'layers.hip', 'net.hip', 'retinaface_post.hip', 'arcface_post.hip',
-           'openpose_post.hip']
+           'openpose_post.hip', 'draw.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 
@@ -63,7 +63,8 @@ def build(force=False, verbose=False):
             continue
         o = os.path.join(CSRC, src.replace('.hip', '.o'))
         objs.append(o)
-        flags = FLAGS + (['-ffp-contract=off'] if src.endswith('_post.hip') else []) + extra_all   # _post: bit-exact float steps
+        exact = src.endswith('_post.hip') or src == 'draw.hip'        # bit-exact float steps (draw: Pillow's polygon scan)
+        flags = FLAGS + (['-ffp-contract=off'] if exact else []) + extra_all
         want = _unit_hash(s, headers, flags)
         try:
             with open(o + '.stamp') as fh:

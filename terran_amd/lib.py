@@ -50,6 +50,7 @@ SIGNATURES = {
     'ta_frames_resize': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p)]),
     'ta_frames_resize_bicubic': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p)]),
     'ta_frames_paste': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
+    'ta_frames_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_model_load': (c_int, [c_void_p, c_int, c_void_p, c_size_t, P(c_void_p)]),
     'ta_model_free': (None, [c_void_p]),
     'ta_model_kind': (c_int, [c_void_p]),
@@ -81,6 +82,12 @@ SIGNATURES = {
     'ta_debug_conv_counts': (c_int, [c_void_p, c_void_p, c_int]),
     'ta_debug_kernel_work': (c_int, [c_void_p, C.c_char_p, c_size_t, c_int]),
 }
+
+# ta_draw_prim (include/terran_amd.h) and its kinds TA_DRAW_*
+DRAW_BAR, DRAW_LINE, DRAW_DISC = 0, 1, 2
+PRIM_DT = np.dtype([('frame', '<i4'), ('kind', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'),
+                    ('width', '<i4'), ('rgba', 'u1', (4,))])
+assert PRIM_DT.itemsize == 32
 
 # conv kernel variants (include/terran_amd.h TA_CONV_*)
 CONV_VARIANTS = {'auto': 0, 'generic': 1, 'pipe64': 2, 'pipe128': 3, 'split_2x2': 4, 'split_2x2_p8': 5, 'split_2x4': 6,
@@ -315,6 +322,13 @@ class Frames:
 
     def paste(self, src, src_index, dst_index, top, left):
         self.ctx.check(self.ctx.lib.ta_frames_paste(self.ctx.h, src.h, src_index, self.h, dst_index, top, left))
+
+    def draw(self, prims, ctx=None):
+        """Draw `prims` (a PRIM_DT array, in order) into this batch in place (ta_frames_draw).  `ctx`: the context the
+        drawing runs on -- the CALLER's, as in `resize`."""
+        ctx = ctx or self.ctx
+        prims = np.ascontiguousarray(prims, dtype=PRIM_DT)
+        ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, ptr(prims) if len(prims) else None, len(prims)))
 
     def download(self):
         out = np.empty(self.shape, np.uint8)
