@@ -20,7 +20,8 @@
  *     `required` out-value; TA_E_CAPACITY is returned (nothing truncated silently) when too small.
  *   - one ta_ctx per GPU; a ctx and everything created from it belong to ONE host thread.
  *   - there is NO CPU fallback: every entry point fails with TA_E_DEVICE when no gfx950 device
- *     is usable.
+ *     is usable.  One exception: ta_jpeg_coefficients (the host half of the JPEG decoder, no pixels)
+ *     needs no context and no device.
  */
 #ifndef TERRAN_AMD_H
 #define TERRAN_AMD_H
@@ -121,6 +122,59 @@ typedef struct ta_draw_prim {
   uint8_t rgba[4];     /* ink and alpha                             */
 } ta_draw_prim;
 int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n);
+
+/* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
+/* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
+ * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart
+ * intervals, the standard Huffman tables where a file defines none (Motion-JPEG frames).  The markers and the Huffman
+ * stream are decoded on the host; dequantisation, the 8x8 inverse DCT
+ * (libjpeg's JDCT_ISLOW with its range-limit table), fancy upsampling and the YCbCr -> RGB tables run on the device.
+ * Pixels equal libjpeg-turbo's default decode bit for bit.  Anything else is a FALLBACK image, decided on the host from
+ * its markers before any GPU work: its path says why, and the caller decodes it with Pillow. */
+#define TA_JPEG_DEVICE 0                 /* decoded by this library                                                  */
+#define TA_JPEG_FALLBACK_PROCESS 1       /* progressive, lossless or hierarchical                                    */
+#define TA_JPEG_FALLBACK_ARITHMETIC 2    /* arithmetic-coded                                                         */
+#define TA_JPEG_FALLBACK_PRECISION 3     /* samples of other than 8 bits                                             */
+#define TA_JPEG_FALLBACK_COMPONENTS 4    /* neither 1 nor 3 components (CMYK, YCCK)                                  */
+#define TA_JPEG_FALLBACK_COLOR 5         /* 3 components stored as RGB (Adobe transform 0, or component ids R, G, B) */
+#define TA_JPEG_FALLBACK_SCANS 6         /* the components are not all in one interleaved scan                       */
+#define TA_JPEG_FALLBACK_SAMPLING 7      /* a sampling ratio other than 1 or 2                                       */
+#define TA_JPEG_INVALID (-1)             /* ta_jpeg_decode failed with TA_E_INVALID: this image is malformed or truncated  */
+typedef struct ta_jpeg_header {
+  int32_t width, height, components;
+  int32_t path;                        /* TA_JPEG_DEVICE or a TA_JPEG_FALLBACK_* reason                              */
+  int32_t h_samp[3], v_samp[3];        /* sampling factors of the components                                         */
+  int32_t quant_index[3];              /* quantisation table of each component (row of `quant`)                      */
+  int32_t blocks_w[3], blocks_h[3];    /* coefficient block grid of each component (whole MCUs)                      */
+  int32_t restart_interval;            /* MCUs, 0 = none                                                             */
+  int32_t reserved[2];
+  int64_t block_offset[3];             /* first block of each component in the coefficient array                     */
+  int64_t blocks_total;
+  uint16_t quant[4][64];               /* quantisation tables, natural (row-major) order                             */
+} ta_jpeg_header;
+/* HOST ONLY -- the one entry point that needs no context and no device (the exception to "no CPU fallback"; it decodes
+ * no pixels): parses one JPEG and entropy-decodes it into header->blocks_total blocks of 64 int16 quantised
+ * coefficients in natural order, component after component, each component's block grid in raster order.  coefs may be
+ * NULL (header only); capacity_blocks < blocks_total gives TA_E_CAPACITY with the header filled in.  A fallback image
+ * returns TA_OK with its path and whatever header facts were read, and no coefficients.  Malformed or truncated data:
+ * TA_E_INVALID with the reason in err (may be NULL). */
+int ta_jpeg_coefficients(const uint8_t* data, size_t size, ta_jpeg_header* header, int16_t* coefs, int64_t capacity_blocks,
+                         char* err, int err_capacity);
+/* Decodes n JPEGs (data[i], sizes[i] bytes) into resident frames.  All images of one size -- an MJPEG or burst batch --
+ * give ONE (n,H,W,3) batch in out[0] (*required = 1); otherwise out[i] is a (1,H_i,W_i,3) batch per image
+ * (*required = n).  capacity < *required: TA_E_CAPACITY before any work.  paths[i] (n entries) gets TA_JPEG_DEVICE or
+ * the image's TA_JPEG_FALLBACK_* reason; a fallback image's pixels are left zero for the caller to fill
+ * (ta_frames_paste).  The Huffman streams are decoded on `threads` host threads (0: min(n, 16); at most 16) straight
+ * into the context's pinned staging; both kernels run once for the whole call.  Returns when the frames are written.
+ * TA_E_INVALID: not a JPEG, malformed or truncated data; no frames are returned then, ta_last_error names the first
+ * such image and paths[i] is TA_JPEG_INVALID for every one of them (the rest as above), so a caller can hand those to a
+ * more lenient decoder and decode the others again. */
+int ta_jpeg_decode(ta_ctx* ctx, const uint8_t* const* data, const size_t* sizes, int n, int threads, int capacity,
+                   ta_frames** out, int32_t* paths, int32_t* required);
+/* Figures of the last ta_jpeg_decode on this context.  ms[4]: host parse + Huffman wall time, host-to-device copy, then
+ * the dequantise + IDCT kernel and the upsample + colour kernel (HIP events; 0 unless ta_profile_enable is on).
+ * counts[4]: images decoded on the device, coefficient blocks, bytes copied to the device, fallback images. */
+int ta_jpeg_last_stats(const ta_ctx* ctx, double* ms, int64_t* counts);
 
 /* ---- models ---------------------------------------------------------------------------- */
 /* `blob` is the packed model produced by terran_amd/pack.py from a Terran state_dict

@@ -213,6 +213,18 @@ class ArcFace(runtime.RangeFallback):
             mats = align_matrices(np.array([face['landmarks'] for f in faces_per_image for face in f]))
             return np.split(self.embed_faces(images, idx, mats), np.cumsum(counts)[:-1], axis=0)
         n_images = len(images)
+        resident = isinstance(images, (list, tuple)) and any(isinstance(im, lib.Frames) for im in images)
+        if resident and not all(isinstance(im, lib.Frames) and im.shape[0] == 1 for im in images):
+            raise ValueError('a list of resident frames must hold single-image lib.Frames batches only')
+        if resident and faces_per_image is not None:
+            # a list of resident single-image batches (image.open_images, mixed sizes): every face in one launch
+            counts = [len(f) for f in faces_per_image]
+            if sum(counts) == 0:
+                return [np.empty((0, 512)) for _ in range(n_images)]      # float64, as wrapper.py:160-164
+            src = np.repeat(np.arange(n_images), counts)
+            mats = align_matrices(np.array([face['landmarks'] for f in faces_per_image for face in f]))
+            feats = self.embed_faces_multi(list(images), src, np.zeros(len(src), np.int32), mats)
+            return np.split(feats, np.cumsum(counts)[:-1], axis=0)
         if faces_per_image is not None:
             counts = [len(f) for f in faces_per_image]
             total = sum(counts)
@@ -243,11 +255,11 @@ class ArcFace(runtime.RangeFallback):
         canvas = lib.Frames.zeros(self.ctx, n_images, 112, 112)
         try:
             for i, image in enumerate(images):
-                image = np.asarray(image)
-                h, w = image.shape[:2]
+                image = image if resident else np.asarray(image)
+                h, w = image.shape[1:3] if resident else image.shape[:2]
                 scale = 112 / max(w, h)
                 nw, nh = int(w * scale), int(h * scale)
-                src = self.ctx.upload(image[None])
+                src = image if resident else self.ctx.upload(image[None])
                 try:
                     small = src.resize_bicubic(nh, nw)
                     try:
@@ -255,7 +267,8 @@ class ArcFace(runtime.RangeFallback):
                     finally:
                         small.free()
                 finally:
-                    src.free()
+                    if not resident:
+                        src.free()
             return self.embed_faces(canvas, np.arange(n_images), np.tile(_IDENTITY, (n_images, 1)))
         finally:
             canvas.free()

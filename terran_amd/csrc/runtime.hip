@@ -623,3 +623,8 @@ int ta_frames_paste(ta_ctx* ctx, const ta_frames* src, int src_index, ta_frames*
 }
 
 }  // extern "C"
+
+int ta_frames_alloc_uninit(ta_ctx* ctx, int n, int h, int w, ta_frames** out) {
+  ta_enter(ctx);
+  return frames_alloc(ctx, n, h, w, false, out);
+}

@@ -121,6 +121,8 @@ struct ta_ctx {
   std::vector<std::pair<size_t, void*>> frame_cache;
   size_t frame_cache_bytes = 0;
   int64_t pose_peaks = 0, pose_connections = 0;    // statistics of the last OpenPose grouping on this context
+  double jpeg_ms[4] = {0, 0, 0, 0};                // figures of the last ta_jpeg_decode (ta_jpeg_last_stats)
+  int64_t jpeg_counts[4] = {0, 0, 0, 0};
   float* pose_wphase = nullptr;                    // x8 bicubic phase weights on the device (uploaded once per context)
   // where the last grouping left its per-stage results in the scratch block (ta_openpose_debug_read); n = 0: none
   struct {
@@ -242,6 +244,7 @@ struct ta_frames {
   uint8_t* dev;
   size_t cap = 0;          // bytes allocated
 };
+int ta_frames_alloc_uninit(ta_ctx* ctx, int n, int h, int w, ta_frames** out);   // ta_frames_alloc without the zero fill
 
 // ---------------------------------------------------------------------------------------------
 // Planned tensors / kernels

@@ -21,6 +21,16 @@ def _is_single(images):
     return not isinstance(images, (list, tuple)) and len(images.shape) == 3
 
 
+def _resident_list(images):
+    """True for a list of resident single-image batches (what `image.open_images` returns for mixed sizes).  Such a list
+    has the semantics of the list of host images it holds: per-image resize, pad-merge, un-pad and un-scale."""
+    if not isinstance(images, (list, tuple)) or not any(isinstance(im, lib.Frames) for im in images):
+        return False
+    if not all(isinstance(im, lib.Frames) and im.shape[0] == 1 for im in images):
+        raise ValueError('a list of resident frames must hold single-image lib.Frames batches only')
+    return True
+
+
 def _pads(shapes, canvas=None):
     """Per image ((top,bottom),(left,right)) to the max size; the odd pixel goes top/left.
     `canvas` = (mh, mw) of the WHOLE list when this call only sees a shard of it (`_Fanout`)."""
@@ -170,6 +180,8 @@ class Detection:
             images = np.expand_dims(images, 0)
         if self._fanout is not None:
             kw = {}
+            if _resident_list(images):
+                raise ValueError('a batch that is already resident on one device cannot be fanned out: pass host frames')
             if not isinstance(images, (np.ndarray, ShardedFrames)):     # list: every shard pads to the WHOLE list's canvas
                 if self._merge_error is not None:
                     raise self._merge_error
@@ -187,9 +199,10 @@ class Detection:
         else:
             if self._merge_error is not None:
                 raise self._merge_error
+            _resident_list(images)                                       # all resident or none
             singles, scales = [], []
             for im in images:
-                f, s = self._resized(ctx, np.asarray(im)[None])
+                f, s = self._resized(ctx, im if isinstance(im, lib.Frames) else np.asarray(im)[None])
                 singles.append(f)
                 scales.append(s)
             frames, pads = _merge(ctx, singles, _canvas)
@@ -257,6 +270,8 @@ class Recognition:
         if self._fanout is not None and faces_per_image is None and isinstance(images, ShardedFrames):
             raise ValueError('a scattered frame batch needs `faces_per_image` (pre-cropped faces go in as a host list)')
         if self._fanout is not None and faces_per_image is not None:
+            if _resident_list(images):
+                raise ValueError('a batch that is already resident on one device cannot be fanned out: pass host frames')
             out = self._fanout(images if isinstance(images, ShardedFrames) else list(images), list(faces_per_image))
             if any(len(f) for f in faces_per_image):                    # a shard without faces answers float64 (0,512)
                 out = [o.astype(np.float32) if o.shape[0] == 0 else o for o in out]   # (wrapper.py:160-164); 1-way: float32
@@ -307,6 +322,8 @@ class Estimation:
             images = np.expand_dims(images, 0)
         if self._fanout is not None:
             kw = {}
+            if _resident_list(images):
+                raise ValueError('a batch that is already resident on one device cannot be fanned out: pass host frames')
             if not isinstance(images, (np.ndarray, ShardedFrames)):
                 if self._merge_error is not None:
                     raise self._merge_error
@@ -326,10 +343,12 @@ class Estimation:
         else:
             if self._merge_error is not None:
                 raise self._merge_error
-            singles = [ctx.upload(np.asarray(im)[None]) for im in images]
+            _resident_list(images)                                       # all resident or none
+            singles = [im if isinstance(im, lib.Frames) else ctx.upload(np.asarray(im)[None]) for im in images]
             frames, pads = _merge(ctx, singles, _canvas)
-            for f in singles:
-                f.free()
+            for f, im in zip(singles, images):
+                if f is not im:                                  # the caller's resident frames stay
+                    f.free()
         try:
             out = self.model.call_frames(frames)
         finally:

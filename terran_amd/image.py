@@ -1,0 +1,170 @@
+"""Image files in: the reference's `terran.io.open_image`, and JPEG decoding into resident frames on the GPU.
+
+`open_image(uri)` keeps the reference's signature and return value (terran/io/image.py:17-52): a host uint8 (H, W, 3)
+RGB array, Pillow's `Image.open(f).convert('RGB')`, for a path or `pathlib.Path` (URLs are not fetched).
+
+`open_images(items)` / `decode_jpeg(buffers)` return RESIDENT frames for the facades (`Detection`, `Recognition`,
+`Estimation` take a `lib.Frames` batch or a list of single-frame ones): one (n, H, W, 3) `lib.Frames` when every image has
+the same size (an MJPEG or burst batch), else a list of (1, H_i, W_i, 3) `lib.Frames`, in input order.  Baseline JPEGs
+are decoded by `ta_jpeg_decode` -- Huffman on up to 16 host threads, dequantisation, IDCT, upsampling and colour on the
+device -- with the pixels of `open_image` bit for bit.  Every other JPEG (progressive, CMYK, ...) and every other format
+(PNG, ...) is decoded by Pillow and uploaded, so these calls accept what `open_image` accepts.  Each returned batch
+carries `decode_paths`: per image lib.JPEG_DEVICE (0) or the reason it took Pillow (a TA_JPEG_FALLBACK_* code;
+lib.JPEG_INVALID (-1) for a JPEG the library's strict decoder refused -- libjpeg accepts some such files with a warning,
+and Pillow then decodes it or raises as `open_image` would; NOT_JPEG (-2) for another format).  Pillow is imported only
+when such an image comes along.  No EXIF orientation is applied (the reference applies none).
+"""
+import os
+from pathlib import Path
+from urllib.parse import urlparse
+
+import numpy as np
+
+from . import lib, runtime
+
+NOT_JPEG = -2                    # decode_paths of a file that is not a JPEG (lib.JPEG_INVALID = -1: a JPEG the library
+                                 # refused as malformed, decoded by Pillow)
+
+
+def _pillow_rgb(source):
+    """The reference's decode: Pillow, convert('RGB'), grayscale stacked to 3 channels.  `source`: path or file object."""
+    from PIL import Image                     # optional dependency: only the fallback needs it
+    image = np.asarray(Image.open(source).convert('RGB'))
+    if len(image.shape) == 2:
+        image = np.stack([image] * 3, axis=-1)
+    return image
+
+
+def _path(uri):
+    if isinstance(uri, Path):
+        return uri
+    if urlparse(str(uri)).scheme and not os.path.exists(str(uri)):
+        raise ValueError('terran_amd.image does not fetch URLs: %r' % (uri,))
+    return Path(uri).expanduser()
+
+
+def open_image(uri):
+    """terran.io.open_image: the image at `uri` (str or pathlib.Path) as an (H, W, 3) uint8 RGB ndarray."""
+    return _pillow_rgb(_path(uri))
+
+
+def _read(item):
+    if isinstance(item, (bytes, bytearray, memoryview)):
+        return bytes(item)
+    with open(_path(item), 'rb') as fh:
+        return fh.read()
+
+
+def _is_jpeg(data):
+    return len(data) >= 2 and data[0] == 0xFF and data[1] == 0xD8
+
+
+def decode_jpeg(buffers, ctx=None, threads=0):
+    """JPEG byte strings -> resident frames (see the module doc); `threads`: host threads for the Huffman decode
+    (0 = min(n, 16))."""
+    return open_images(list(buffers), ctx=ctx, threads=threads)
+
+
+def open_images(uris_or_bytes, device=None, ctx=None, threads=0):
+    """Paths, `pathlib.Path`s or encoded bytes -> one resident `lib.Frames` (all images of one size) or a list of
+    single-image `lib.Frames` (mixed sizes), in input order."""
+    ctx = ctx if ctx is not None else runtime.get_context(device)
+    datas = [_read(x) for x in uris_or_bytes]
+    n = len(datas)
+    if n == 0:
+        raise ValueError('open_images: no images')
+    paths = np.full(n, NOT_JPEG, np.int32)
+    jpeg_idx = [i for i, d in enumerate(datas) if _is_jpeg(d)]
+    host = {i: _pillow_rgb(_BytesIO(d)) for i, d in enumerate(datas) if not _is_jpeg(d)}   # other formats: Pillow
+    outs, jp, jpeg_idx = _decode_jpegs(ctx, datas, jpeg_idx, threads, paths)
+    for i in np.nonzero(paths == lib.JPEG_INVALID)[0]:
+        # refused by the library's strict decoder (libjpeg only warns about e.g. a missing restart marker): Pillow
+        # decodes it or raises, exactly as open_image would
+        try:
+            host[int(i)] = _pillow_rgb(_BytesIO(datas[i]))
+        except Exception:
+            _free(outs)
+            raise
+    if not host:
+        # the common case: every image went to the library -- it shaped the output; fallback images are filled in place
+        try:
+            for k in np.nonzero(jp != lib.JPEG_DEVICE)[0]:
+                dst, slot = (outs[0], int(k)) if len(outs) == 1 else (outs[int(k)], 0)
+                _paste_host(ctx, _pillow_rgb(_BytesIO(datas[jpeg_idx[k]])), dst, slot)
+        except Exception:
+            _free(outs)
+            raise
+        return _tag(outs, paths)
+    # some images came from Pillow: lay every image out anew
+    dev = {i: ((outs[0], k) if len(outs) == 1 else (outs[k], 0)) for k, i in enumerate(jpeg_idx)}
+    result = []
+    try:
+        shapes = [host[i].shape[:2] if i in host else dev[i][0].shape[1:3] for i in range(n)]
+        same = all(s == shapes[0] for s in shapes)
+        if same:
+            result.append(lib.Frames.zeros(ctx, n, *shapes[0]))
+        else:
+            for s in shapes:
+                result.append(lib.Frames.zeros(ctx, 1, *s))
+        for i in range(n):
+            dst, k = (result[0], i) if same else (result[i], 0)
+            if i in host:
+                _paste_host(ctx, host[i], dst, k)
+            elif paths[i] != lib.JPEG_DEVICE:
+                _paste_host(ctx, _pillow_rgb(_BytesIO(datas[i])), dst, k)
+            else:
+                dst.paste(dev[i][0], dev[i][1], k, 0, 0)
+    except Exception:
+        _free(result)
+        raise
+    finally:
+        _free(outs)
+    return _tag(result, paths)
+
+
+def _decode_jpegs(ctx, datas, idx, threads, paths):
+    """ta_jpeg_decode over datas[idx] -> (frames, per-image paths, the indices decoded).  Images the library refuses as
+    malformed are marked JPEG_INVALID in `paths` and the others decoded again without them."""
+    if not idx:
+        return [], np.zeros(0, np.int32), []
+    try:
+        outs, jp = ctx.jpeg_decode([datas[i] for i in idx], threads)
+    except lib.TerranAmdError as e:
+        bad = getattr(e, 'paths', None)
+        if e.code != lib.E_INVALID or bad is None or not (bad == lib.JPEG_INVALID).any():
+            raise
+        for k in np.nonzero(bad == lib.JPEG_INVALID)[0]:
+            paths[idx[k]] = lib.JPEG_INVALID
+        idx = [i for k, i in enumerate(idx) if bad[k] != lib.JPEG_INVALID]
+        if not idx:
+            return [], np.zeros(0, np.int32), []
+        outs, jp = ctx.jpeg_decode([datas[i] for i in idx], threads)
+    paths[idx] = jp
+    return outs, jp, idx
+
+
+def _free(frames):
+    for f in frames:
+        f.free()
+
+
+def _BytesIO(data):
+    import io
+    return io.BytesIO(data)
+
+
+def _paste_host(ctx, pixels, dst, index):
+    src = ctx.upload(pixels[None])
+    try:
+        dst.paste(src, 0, index, 0, 0)
+    finally:
+        src.free()
+
+
+def _tag(frames, paths):
+    if len(frames) == 1 and frames[0].shape[0] == len(paths):
+        frames[0].decode_paths = paths
+        return frames[0]
+    for f, p in zip(frames, paths):
+        f.decode_paths = np.array([p], np.int32)
+    return frames

@@ -51,6 +51,10 @@ SIGNATURES = {
     'ta_frames_resize_bicubic': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p)]),
     'ta_frames_paste': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
     'ta_frames_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
+    'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
+                               P(C.c_int32)]),
+    'ta_jpeg_last_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
     'ta_model_load': (c_int, [c_void_p, c_int, c_void_p, c_size_t, P(c_void_p)]),
     'ta_model_free': (None, [c_void_p]),
     'ta_model_kind': (c_int, [c_void_p]),
@@ -88,6 +92,39 @@ DRAW_BAR, DRAW_LINE, DRAW_DISC = 0, 1, 2
 PRIM_DT = np.dtype([('frame', '<i4'), ('kind', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'),
                     ('width', '<i4'), ('rgba', 'u1', (4,))])
 assert PRIM_DT.itemsize == 32
+
+# ta_jpeg_header and the decode paths TA_JPEG_* (include/terran_amd.h)
+JPEG_DEVICE = 0
+JPEG_INVALID = -1
+JPEG_PATHS = {-1: 'invalid', 0: 'device', 1: 'progressive/lossless/hierarchical', 2: 'arithmetic', 3: 'precision',
+              4: 'components', 5: 'rgb', 6: 'scans', 7: 'sampling'}
+JPEG_HEADER_DT = np.dtype([('width', '<i4'), ('height', '<i4'), ('components', '<i4'), ('path', '<i4'),
+                           ('h_samp', '<i4', (3,)), ('v_samp', '<i4', (3,)), ('quant_index', '<i4', (3,)),
+                           ('blocks_w', '<i4', (3,)), ('blocks_h', '<i4', (3,)), ('restart_interval', '<i4'),
+                           ('reserved', '<i4', (2,)), ('block_offset', '<i8', (3,)), ('blocks_total', '<i8'),
+                           ('quant', '<u2', (4, 64))])
+assert JPEG_HEADER_DT.itemsize == 632
+
+
+def jpeg_coefficients(data, header_only=False):
+    """Host only (no context, no device): ta_jpeg_coefficients -> (header record of JPEG_HEADER_DT, int16
+    (blocks_total, 64) quantised coefficients in natural order, or None for a fallback image / header_only).
+    Raises TerranAmdError(TA_E_INVALID) on malformed data."""
+    lib = load()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    hdr = np.zeros(1, JPEG_HEADER_DT)
+    err = C.create_string_buffer(256)
+    rc = lib.ta_jpeg_coefficients(ptr(buf), buf.size, ptr(hdr), None, 0, err, len(err))
+    if rc != OK:
+        raise TerranAmdError(rc, err.value.decode(errors='replace'))
+    if header_only or hdr['path'][0] != JPEG_DEVICE:
+        return hdr[0], None
+    coefs = np.empty((int(hdr['blocks_total'][0]), 64), np.int16)
+    rc = lib.ta_jpeg_coefficients(ptr(buf), buf.size, ptr(hdr), ptr(coefs), coefs.shape[0], err, len(err))
+    if rc != OK:
+        raise TerranAmdError(rc, err.value.decode(errors='replace'))
+    return hdr[0], coefs
+
 
 # conv kernel variants (include/terran_amd.h TA_CONV_*)
 CONV_VARIANTS = {'auto': 0, 'generic': 1, 'pipe64': 2, 'pipe128': 3, 'split_2x2': 4, 'split_2x2_p8': 5, 'split_2x4': 6,
@@ -224,6 +261,33 @@ class Context:
         out = np.empty((a.shape[0], b.shape[0]), np.float32)
         self.check(self.lib.ta_cosine_distance(self.h, ptr(a), a.shape[0], ptr(b), b.shape[0], a.shape[1], ptr(out)))
         return out
+
+    def jpeg_decode(self, buffers, threads=0):
+        """ta_jpeg_decode: JPEG byte strings -> (list of resident Frames, paths).  One (n,H,W,3) batch when every image
+        has the same size, else one (1,H_i,W_i,3) batch per image; paths[i] is JPEG_DEVICE or the fallback reason
+        (that image's pixels are zero: the caller fills them).  A TerranAmdError(E_INVALID) carries `.paths`."""
+        bufs = [bytes(b) for b in buffers]
+        n = len(bufs)
+        arrs = [np.frombuffer(b, np.uint8) for b in bufs]
+        data = (c_void_p * n)(*[a.ctypes.data for a in arrs])
+        sizes = (c_size_t * n)(*[a.size for a in arrs])
+        out = (c_void_p * n)()
+        paths = np.zeros(n, np.int32)
+        req = C.c_int32()
+        rc = self.lib.ta_jpeg_decode(self.h, data, sizes, n, int(threads), n, out, paths.ctypes.data_as(P(C.c_int32)),
+                                     C.byref(req))
+        if rc != OK:
+            e = TerranAmdError(rc, self.last_error())
+            e.paths = paths                             # TA_E_INVALID: JPEG_INVALID marks the malformed images
+            raise e
+        return [Frames(self, handle=c_void_p(out[k])) for k in range(req.value)], paths
+
+    def jpeg_stats(self):
+        """Figures of the last jpeg_decode: ({host, h2d, idct, color}: ms), {images, blocks, bytes, fallbacks}."""
+        ms, cnt = np.zeros(4, np.float64), np.zeros(4, np.int64)
+        self.check(self.lib.ta_jpeg_last_stats(self.h, ptr(ms), ptr(cnt)))
+        return (dict(zip(('host', 'h2d', 'idct', 'color'), ms.tolist())),
+                dict(zip(('images', 'blocks', 'bytes', 'fallbacks'), cnt.tolist())))
 
     def conv_variant(self, name):
         """Debug: force every following conv on this context onto one kernel variant ('auto' to release)."""
