@@ -176,6 +176,26 @@ int ta_jpeg_decode(ta_ctx* ctx, const uint8_t* const* data, const size_t* sizes,
  * counts[4]: images decoded on the device, coefficient blocks, bytes copied to the device, fallback images. */
 int ta_jpeg_last_stats(const ta_ctx* ctx, double* ms, int64_t* counts);
 
+/* ---- JPEG encode (Image.fromarray(frame).save(f, 'JPEG', quality=q, subsampling=s) with Pillow's other defaults) ---- */
+/* Baseline JFIF files byte for byte as Pillow / libjpeg-turbo writes them: Annex K quantisation tables scaled by
+ * `quality` (1..100, force_baseline), islow forward DCT, standard Huffman tables, no restart markers, no smoothing.
+ * subsampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's default).  Progressive, optimized Huffman tables, custom
+ * quantisation tables, restart intervals and metadata segments are not offered. */
+/* HOST ONLY, no context: the header Pillow writes for an h x w RGB image (SOI .. SOS).  *size gets its length; capacity
+ * < *size gives TA_E_CAPACITY.  Bad arguments: TA_E_INVALID. */
+int ta_jpeg_encode_header(int h, int w, int quality, int subsampling, uint8_t* out, size_t capacity, size_t* size);
+/* frames -> n complete JPEG files, back to back in context-owned pinned memory (*out) that stays valid until the next
+ * ta_jpeg_encode on ctx; sizes[i] bytes each (n entries).  Runs on ctx's stream, after whatever was queued there (a
+ * ta_frames_draw, say); every stage runs on the device and only the files are copied back.  Returns when they are
+ * there.  Bad arguments: TA_E_INVALID before any launch. */
+int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, const uint8_t** out,
+                   size_t* sizes);
+/* Figures of the last ta_jpeg_encode on this context.  ms[8]: HIP-event times (0 unless ta_profile_enable is on) of the
+ * staging copy, E1 (pixels -> coefficients), E2 (bit lengths + scan), E3 (emit), E4a (0xFF count + scan), E4b (stuff +
+ * pack), the device-to-host copy of the files; then the host wall time of the whole call.  counts[4]: images, blocks,
+ * bytes copied to the host, entropy-coded bytes before stuffing. */
+int ta_jpeg_encode_last_stats(const ta_ctx* ctx, double* ms, int64_t* counts);
+
 /* ---- models ---------------------------------------------------------------------------- */
 /* `blob` is the packed model produced by terran_amd/pack.py from a Terran state_dict
  * (replaces load_model(): retinaface/wrapper.py:16-22, arcface/wrapper.py:13-19,

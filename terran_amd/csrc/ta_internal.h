@@ -123,6 +123,12 @@ struct ta_ctx {
   int64_t pose_peaks = 0, pose_connections = 0;    // statistics of the last OpenPose grouping on this context
   double jpeg_ms[4] = {0, 0, 0, 0};                // figures of the last ta_jpeg_decode (ta_jpeg_last_stats)
   int64_t jpeg_counts[4] = {0, 0, 0, 0};
+  double jpeg_enc_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // figures of the last ta_jpeg_encode (ta_jpeg_encode_last_stats)
+  int64_t jpeg_enc_counts[4] = {0, 0, 0, 0};
+  void* jpeg_enc_dev = nullptr;                    // ta_jpeg_encode's second device block (bit words + packed files), grow-only
+  size_t jpeg_enc_dev_bytes = 0;
+  uint8_t* jpeg_enc_out = nullptr;                 // pinned: the files of the last ta_jpeg_encode, grow-only
+  size_t jpeg_enc_out_bytes = 0;
   float* pose_wphase = nullptr;                    // x8 bicubic phase weights on the device (uploaded once per context)
   // where the last grouping left its per-stage results in the scratch block (ta_openpose_debug_read); n = 0: none
   struct {

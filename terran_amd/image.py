@@ -13,6 +13,12 @@ carries `decode_paths`: per image lib.JPEG_DEVICE (0) or the reason it took Pill
 lib.JPEG_INVALID (-1) for a JPEG the library's strict decoder refused -- libjpeg accepts some such files with a warning,
 and Pillow then decodes it or raises as `open_image` would; NOT_JPEG (-2) for another format).  Pillow is imported only
 when such an image comes along.  No EXIF orientation is applied (the reference applies none).
+
+Out: `encode_jpeg(images, quality, subsampling)` encodes resident batches (or host arrays, uploaded first) on the GPU
+(`ta_jpeg_encode`) into JPEG files that are byte for byte what Pillow's `Image.fromarray(frame).save(f, 'JPEG',
+quality=quality, subsampling=subsampling)` writes; only the compressed bytes leave the device.  `save_images` writes
+them to files.  Pillow's argument semantics: quality 1..100 (default 75), subsampling -1 (default: 4:2:0), 0 / '4:4:4',
+1 / '4:2:2', 2 / '4:2:0'.  Other options (progressive, optimize, qtables, dpi, exif, ...) are not offered.
 """
 import os
 from pathlib import Path
@@ -168,3 +174,67 @@ def _tag(frames, paths):
     for f, p in zip(frames, paths):
         f.decode_paths = np.array([p], np.int32)
     return frames
+
+
+_SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}
+
+
+def jpeg_options(quality=75, subsampling=-1):
+    """Pillow's save() arguments -> (quality, subsampling code for ta_jpeg_encode); ValueError for anything else."""
+    key = subsampling if isinstance(subsampling, str) else (
+        int(subsampling) if isinstance(subsampling, (int, np.integer)) and not isinstance(subsampling, bool) else None)
+    if key not in _SUBSAMPLING:
+        raise ValueError('subsampling must be -1, 0, 1, 2, \'4:4:4\', \'4:2:2\' or \'4:2:0\', got %r' % (subsampling,))
+    return lib.check_jpeg_options(quality, _SUBSAMPLING[key])
+
+
+def encode_jpeg(images, quality=75, subsampling=-1, ctx=None, device=None):
+    """Resident frames -> JPEG files (list of bytes, one per frame, in order).  `images`: a `lib.Frames` batch, a list of
+    them (as `open_images` returns for mixed sizes), or a host uint8 (H, W, 3) / (N, H, W, 3) array (uploaded first).
+    Every option is checked before anything is launched."""
+    quality, code = jpeg_options(quality, subsampling)
+    if isinstance(images, lib.Frames):
+        batches = [images]
+    elif isinstance(images, (list, tuple)):
+        batches = list(images)
+        if not batches or not all(isinstance(b, lib.Frames) for b in batches):
+            raise ValueError('encode_jpeg: a list must hold lib.Frames batches')
+    else:
+        arr = np.asarray(images)
+        if arr.dtype != np.uint8 or arr.ndim not in (3, 4) or arr.shape[-1] != 3 or 0 in arr.shape:
+            raise ValueError('encode_jpeg: host images must be uint8 (H, W, 3) or (N, H, W, 3) RGB, got %s %s'
+                             % (arr.dtype, arr.shape))
+        if max(arr.shape[-3:-1]) > 65535:
+            raise ValueError('encode_jpeg: JPEG sides are at most 65535 pixels')
+        ctx = ctx if ctx is not None else runtime.get_context(device)
+        up = ctx.upload(arr[None] if arr.ndim == 3 else arr)
+        try:
+            return ctx.jpeg_encode(up, quality, code)
+        finally:
+            up.free()
+    for b in batches:
+        if max(b.shape[1:3]) > 65535:
+            raise ValueError('encode_jpeg: JPEG sides are at most 65535 pixels')
+    files = []
+    for b in batches:
+        files.extend(b.encode_jpeg(quality, code, ctx=ctx))
+    return files
+
+
+def save_images(images, paths, quality=75, subsampling=-1, ctx=None, device=None):
+    """encode_jpeg(images, ...) written to `paths` (one per frame, in order)."""
+    paths = list(paths)
+    jpeg_options(quality, subsampling)
+    if isinstance(images, lib.Frames):
+        n = images.shape[0]
+    elif isinstance(images, (list, tuple)):
+        n = sum(b.shape[0] for b in images if isinstance(b, lib.Frames))
+    else:
+        shape = np.shape(images)
+        n = 1 if len(shape) == 3 else (shape[0] if shape else 0)
+    if n != len(paths):
+        raise ValueError('save_images: %d frames, %d paths' % (n, len(paths)))
+    files = encode_jpeg(images, quality, subsampling, ctx=ctx, device=device)
+    for data, path in zip(files, paths):
+        with open(_path(path), 'wb') as fh:
+            fh.write(data)

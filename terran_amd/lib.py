@@ -55,6 +55,9 @@ SIGNATURES = {
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
     'ta_jpeg_last_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'ta_jpeg_encode_header': (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(c_size_t)]),
+    'ta_jpeg_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p), P(c_size_t)]),
+    'ta_jpeg_encode_last_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
     'ta_model_load': (c_int, [c_void_p, c_int, c_void_p, c_size_t, P(c_void_p)]),
     'ta_model_free': (None, [c_void_p]),
     'ta_model_kind': (c_int, [c_void_p]),
@@ -124,6 +127,27 @@ def jpeg_coefficients(data, header_only=False):
     if rc != OK:
         raise TerranAmdError(rc, err.value.decode(errors='replace'))
     return hdr[0], coefs
+
+
+def jpeg_encode_header(h, w, quality=75, subsampling=2):
+    """Host only (no context, no device): ta_jpeg_encode_header -> the bytes SOI .. SOS Pillow writes for an h x w RGB
+    image."""
+    lib = load()
+    size = c_size_t()
+    buf = np.zeros(1024, np.uint8)
+    rc = lib.ta_jpeg_encode_header(int(h), int(w), int(quality), int(subsampling), ptr(buf), buf.size, C.byref(size))
+    if rc != OK:
+        raise TerranAmdError(rc, 'jpeg_encode_header(%r, %r, %r, %r)' % (h, w, quality, subsampling))
+    return buf[:size.value].tobytes()
+
+
+def check_jpeg_options(quality, subsampling):
+    """The encoder's options as ints, or ValueError (before anything is launched): quality 1..100, subsampling 0 / 1 / 2."""
+    if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
+        raise ValueError('JPEG quality must be an int in 1..100, got %r' % (quality,))
+    if isinstance(subsampling, bool) or not isinstance(subsampling, (int, np.integer)) or subsampling not in (0, 1, 2):
+        raise ValueError('JPEG subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r' % (subsampling,))
+    return int(quality), int(subsampling)
 
 
 # conv kernel variants (include/terran_amd.h TA_CONV_*)
@@ -289,6 +313,28 @@ class Context:
         return (dict(zip(('host', 'h2d', 'idct', 'color'), ms.tolist())),
                 dict(zip(('images', 'blocks', 'bytes', 'fallbacks'), cnt.tolist())))
 
+    def jpeg_encode(self, frames, quality=75, subsampling=2):
+        """ta_jpeg_encode: a resident Frames batch -> list of JPEG files (bytes), Pillow's for the same options; runs on
+        this context's stream (ordered after a draw on it)."""
+        quality, subsampling = check_jpeg_options(quality, subsampling)
+        n = frames.shape[0]
+        out = c_void_p()
+        sizes = (c_size_t * n)()
+        self.check(self.lib.ta_jpeg_encode(self.h, frames.h, quality, subsampling, C.byref(out), sizes))
+        files, at = [], out.value
+        for k in range(n):
+            files.append(C.string_at(at, sizes[k]))
+            at += sizes[k]
+        return files
+
+    def jpeg_encode_stats(self):
+        """Figures of the last jpeg_encode: ({h2d, coef, length, emit, ffcount, pack, d2h, host}: ms),
+        {images, blocks, bytes, entropy_bytes}."""
+        ms, cnt = np.zeros(8, np.float64), np.zeros(4, np.int64)
+        self.check(self.lib.ta_jpeg_encode_last_stats(self.h, ptr(ms), ptr(cnt)))
+        return (dict(zip(('h2d', 'coef', 'length', 'emit', 'ffcount', 'pack', 'd2h', 'host'), ms.tolist())),
+                dict(zip(('images', 'blocks', 'bytes', 'entropy_bytes'), cnt.tolist())))
+
     def conv_variant(self, name):
         """Debug: force every following conv on this context onto one kernel variant ('auto' to release)."""
         self.check(self.lib.ta_debug_conv_variant(self.h, CONV_VARIANTS[name]))
@@ -393,6 +439,11 @@ class Frames:
         ctx = ctx or self.ctx
         prims = np.ascontiguousarray(prims, dtype=PRIM_DT)
         ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, ptr(prims) if len(prims) else None, len(prims)))
+
+    def encode_jpeg(self, quality=75, subsampling=2, ctx=None):
+        """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs
+        on -- the CALLER's, as in `draw`, so it is ordered after a draw on that context."""
+        return (ctx or self.ctx).jpeg_encode(self, quality, subsampling)
 
     def download(self):
         out = np.empty(self.shape, np.uint8)

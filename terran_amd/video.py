@@ -9,6 +9,10 @@ MI355X-first differences: the thread reads straight into page-locked host buffer
 uploads on its OWN context/stream, so decode, H2D and the previous batch's kernels overlap; what the consumer
 gets is a `lib.Frames` batch already resident in HBM (detection, recognition and pose all read it in place).
 Building the ffmpeg command line (reader.py:421-465) stays Terran's job: pass its `proc.stdout` as `stream`.
+
+The way out mirrors it: `JpegVideoWriter` encodes frames to JPEG on the GPU (terran_amd.image.encode_jpeg, byte for byte
+Pillow's files) and writes them back to back -- a Motion-JPEG elementary stream, what `ffmpeg -f mjpeg -i pipe:` reads --
+to `stream` (a file, or `proc.stdin` of an ffmpeg the caller started).  Only the compressed bytes leave the device.
 """
 import threading
 from queue import Full as QueueFull, Queue
@@ -16,6 +20,7 @@ from queue import Full as QueueFull, Queue
 import numpy as np
 
 DEFAULT_READER_BUFFER_SIZE = 1
+DEFAULT_WRITER_BUFFER_SIZE = 64                 # frames (terran/io/video/__init__.py)
 
 
 class EndOfVideo(Exception):
@@ -140,3 +145,95 @@ class RawVideoReader:
 
     def __exit__(self, *a):
         self.close()
+
+
+class JpegVideoWriter:
+    """Write frames as a Motion-JPEG stream.
+
+        with JpegVideoWriter(proc.stdin, quality=90) as writer:
+            for frames in RawVideoReader(...):
+                faces = face_detection(frames)
+                vis.draw_faces(frames, faces)
+                writer.write_frames(frames)            # encoded where they are; the bytes go to a writer thread
+
+    Encoding runs on the calling thread's context (ordered after a draw on it); a daemon thread writes the files to
+    `stream` through a queue of at most `buffer_size` frames.  A write error is raised by the next call; writing after
+    `close()` raises VideoClosed.  `encoder(images, quality, subsampling) -> list of bytes` replaces the GPU encoder
+    (tests)."""
+
+    def __init__(self, stream, quality=75, subsampling=-1, buffer_size=DEFAULT_WRITER_BUFFER_SIZE, device=None,
+                 encoder=None):
+        from . import image
+        image.jpeg_options(quality, subsampling)            # bad options fail here, before any frame
+        self.stream, self.quality, self.subsampling = stream, quality, subsampling
+        self.frames_written = 0
+        self._device = device
+        self._encoder = encoder
+        self._queue = Queue(max(1, int(buffer_size)))
+        self._error = None
+        self._closed = False
+        self._thread = threading.Thread(target=self._worker, daemon=True)
+        self._thread.start()
+
+    def _worker(self):
+        while True:
+            data = self._queue.get()
+            if data is None:
+                break
+            if self._error is not None:
+                continue                                    # drain: the consumer sees the first error
+            try:
+                self.stream.write(data)
+                self.frames_written += 1
+            except Exception as e:                          # surfaced by the next call
+                self._error = e
+        if self._error is None:
+            try:
+                if hasattr(self.stream, 'flush'):
+                    self.stream.flush()
+            except Exception as e:
+                self._error = e
+
+    def _raise_pending(self):
+        if self._error is not None:
+            e, self._error = self._error, None
+            raise e
+
+    def _encode(self, images):
+        if self._encoder is not None:
+            return self._encoder(images, self.quality, self.subsampling)
+        from . import image
+        return image.encode_jpeg(images, self.quality, self.subsampling, device=self._device)
+
+    def write_frames(self, batch):
+        """Encode every frame of `batch` (a lib.Frames batch, a list of them, or host uint8 (N, H, W, 3)) and queue the
+        files."""
+        if self._closed:
+            raise VideoClosed('The video has already been closed.')
+        self._raise_pending()
+        for data in self._encode(batch):
+            self._queue.put(data)
+
+    def write_frame(self, frame_or_func, *args):
+        """The reference's signature (terran/io/video/writer.py:122-156): a frame, or a function whose result
+        `frame_or_func(*args)` is the frame (a host (H, W, 3) array or a resident batch)."""
+        if self._closed:
+            raise VideoClosed('The video has already been closed.')
+        frame = frame_or_func(*args) if callable(frame_or_func) else frame_or_func
+        self.write_frames(frame)
+
+    def close(self):
+        """Write what is queued, stop the thread; re-raises a pending write error."""
+        if self._closed:
+            raise VideoClosed('The video has already been closed.')
+        self._closed = True
+        self._queue.put(None)
+        self._thread.join()
+        self._raise_pending()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        if not self._closed:
+            self.close()
