@@ -171,10 +171,10 @@ int ta_ctx_create(int device_id, ta_ctx** out) {
     return TA_E_DEVICE;
   }
   *ctx->range_flag_host = 0;
-  // measurement aids for tools/ (the shipped path leaves both unset)
+  // measurement aid for tools/ (the shipped path leaves it unset)
   if (const char* e = getenv("TA_CONV_PREFER")) ctx->conv_force = atoi(e);
-#if defined(TA_TOOLS) || defined(TA_CONV_TRACE)   // timing ablations that give WRONG results (bits 0..7; bits 8.. = the workgroup the trace build stamps): only in a tools build (TA_EXTRA_FLAGS=-DTA_TOOLS), never in the shipped library
-  if (const char* e = getenv("TA_CONV_PROBE")) ctx->conv_probe = atoi(e);
+#ifdef TA_CONV_TRACE
+  if (const char* e = getenv("TA_CONV_TRACE_BLOCK")) ctx->conv_trace_block = atoi(e);
 #endif
   *out = ctx;
   return TA_OK;

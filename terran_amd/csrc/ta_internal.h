@@ -154,7 +154,9 @@ struct ta_ctx {
   // every conv that variant CAN run is launched on (others stay automatic);
   // conv_counts[v] = launches per variant since the last ta_debug_conv_counts(reset)
   int conv_force = 0;
-  int conv_probe = 0;                              // tools only (TA_CONV_PROBE): timing ablations of the split kernel
+#ifdef TA_CONV_TRACE
+  int conv_trace_block = 0;                        // trace build (TA_CONV_TRACE_BLOCK): the workgroup whose cycle stamps are recorded
+#endif
   int64_t conv_counts[16] = {0};
   // f16x3: raised (device side) by a conv epilogue that met |x| > 65504 while writing a half-split tensor; copied to
   // the pinned host word behind the results of a call (ta_range_enqueue) and turned into TA_E_RANGE (ta_range_check)
@@ -289,7 +291,6 @@ struct ta_conv_launch {
   int o2_img, o2_row, o2_pix, o2_off0, o2_ch, o2_fmt;
   int in_fmt;
   int win_wp, win_img;                         // pixels per padded row / per padded image of the INPUT tensor (conv_igemm_win: patch rows)
-  int direct_epilogue;                         // debug A/B: 1 = split kernel stores straight from the accumulators
   int group_cout, group_cin;                   // grouped conv: output channels / input channels per group (0 = dense)
   int k_split;                                 // > 1: K is cut in k_split ranges, one workgroup each; raw sums go to
   float* partial;                              //      partial[k][pixel][coutp] and splitk_reduce_kernel finishes the op
@@ -306,11 +307,10 @@ struct ta_conv_launch {
   // set-up needs no integer division (each one is a ~300-cycle dependent instruction chain in front of the first DMA)
   float r_nct, r_tile_blocks, r_Wo, r_Ho, r_HoWo;
   int fast_div;                                // 1: every dividend of the set-up is < 2^24 (exact in float32)
-  int cons_prio;                               // split-role kernels: s_setprio level of the consumer (MFMA) waves, 0..3 (0 = leave alone)
   int fast_drain;                              // 1: the lean epilogue applies (split-format tensors below 4 GB, cout % 8 == 0, no pool / K-split)
-  int probe;                                   // tools only: bits 0..1: 1 = producers skip the pixel-row DMA after the ring is full,
-                                               //             2 = no DMA at all after the ring is full (WRONG results);
-                                               //             bit 2 (TA_CONV_LATE_B): slab 0's pixel-row DMAs after ALL addresses are computed
+#ifdef TA_CONV_TRACE
+  int trace_block;                             // trace build only: the workgroup that TA_STAMP records (ta_ctx::conv_trace_block)
+#endif
                                                // [bias .. bias + coutp) is followed by the per-channel un-scale vector wus[coutp] (ta_op_desc.wus_off
                                                // == bias_off + 4 coutp): one pointer for both keeps the kernel-argument block (SGPRs) small
   const float* bias9;                          // border-class biases [16][coutp] of a conv with a folded input affine (nullptr: none)
@@ -322,7 +322,7 @@ struct ta_conv_launch {
   int* range_flag;                             // set to 1 by an epilogue that stores |x| > 65504, inf or NaN while range_check is on
 };
 
-// the pre-split activation format the conv kernels of arithmetic mode `prec` read (PREC_* of conv_igemm.hip)
+// the pre-split activation format the conv kernels of arithmetic mode `prec` read (PREC_* of conv_common.h)
 static inline int ta_split_fmt_of(int prec) { return prec == 0 ? 0 /* TA_FMT_F32 */ : (prec == 4 ? 3 /* TA_FMT_F16 */ : ((prec == 3 || prec == 5) ? 2 /* TA_FMT_SPLIT16 */ : 1 /* TA_FMT_SPLIT */)); }
 
 // K-splitting of a conv with a very long K and few output tiles (ArcFace's 25088 -> 512 FC: 784 slabs, 4..8 tiles of
@@ -339,8 +339,19 @@ static inline int ta_conv_ksplit(int coutp, int n_slabs, bool eligible, int pack
   return 32;
 }
 
-int ta_launch_conv(ta_ctx* ctx, const ta_conv_launch& p, double flops);
-int ta_launch_dwpw(ta_ctx* ctx, const ta_conv_launch& p, double flops);
+int ta_launch_conv(ta_ctx* ctx, const ta_conv_launch& p, double flops);   // conv_igemm.hip: checks, kernel choice, then one of:
+// the kernel families, one translation unit each: `variant` is a TA_CV_* of that family that can run the launch
+// (variant_eligible), the arithmetic mode is p.prec; each does the switch to its template instances
+int ta_launch_conv_sym(ta_ctx* ctx, int variant, const ta_conv_launch& p);     // conv_sym.hip: TA_CV_GENERIC, TA_CV_PIPE*
+int ta_launch_conv_split(ta_ctx* ctx, int variant, const ta_conv_launch& p);   // conv_split.hip: TA_CV_SPLIT_*, TA_CV_WIN_*
+int ta_launch_conv_split_modes(ta_ctx* ctx, int variant, const ta_conv_launch& p);   // conv_split_modes.hip: its f32 / bf16x3 / bf16 / f16 instances (called by the above)
+int ta_launch_dwpw(ta_ctx* ctx, const ta_conv_launch& p, double flops);        // conv_dwpw.hip
+// conv_split.hip: patch rows a BM-pixel tile of this launch can need at most, against what the window kernels are
+// instantiated with: patch capacity per tile shape (LDS: 3 weight stages + 2 patches <= 160 KiB)
+int ta_win_patch_rows(const ta_conv_launch& p, int BM);
+#define TA_WIN_PR_2x2 384
+#define TA_WIN_PR_2x4 448
+#define TA_WIN_PR_1x4 512
 struct ta_frames;
 // RetinaFace front kernel: frames (uint8 RGB) -> 16-channel float tensor at half resolution; 448 packed floats in HOST memory
 int ta_launch_rfstem(ta_ctx* ctx, const uint8_t* frames_dev, int n, int h, int w, const float* weights_host, const float* w2_dev, const struct ta_tensor& out);

@@ -2,8 +2,7 @@
 
     python tools/conv_bench.py            # the two shapes that dominate the 1080p workload
 Prints TFLOP/s (algorithmic) per shape and precision.  TA_CONV_PREFER=<TA_CONV_* code> prefers one kernel variant
-wherever it is eligible; TA_CONV_PROBE=1|2 are timing ablations of the split-role kernel (no pixel-row DMA / no DMA at
-all once the LDS ring is full: WRONG results, upper bounds only)."""
+wherever it is eligible."""
 import os
 import sys
 import time

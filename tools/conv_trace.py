@@ -13,7 +13,7 @@ ctx = lib.Context(0)
 k = int(sys.argv[1]) if len(sys.argv) > 1 else 1
 cin, cout = (int(sys.argv[2]), int(sys.argv[3])) if len(sys.argv) > 3 else (128, 128)
 n, h, w = (int(v) for v in sys.argv[4:7]) if len(sys.argv) > 6 else (32, 23, 40)
-prec = sys.argv[7] if len(sys.argv) > 7 else 'f16x3'         # TA_CONV_PROBE=$((block << 8)) picks the stamped workgroup
+prec = sys.argv[7] if len(sys.argv) > 7 else 'f16x3'         # TA_CONV_TRACE_BLOCK=<block> picks the stamped workgroup
 rng = np.random.default_rng(0)
 P = pack.Program(pack.MODEL_OPENPOSE, prec)
 t0 = P.tensor(4, 1)
@@ -31,8 +31,10 @@ for _ in range(3):
     m.forward_frames(fr)
 ctx.sync()
 buf = (C.c_longlong * 16)()
-ctx.lib.ta_debug_trace_read.argtypes = [C.c_void_p, C.c_int]
-assert ctx.lib.ta_debug_trace_read(buf, 16) == 0
+# the stamps of the split-role unit that holds this mode's kernels: conv_split.hip (f16x3, f16x2) or conv_split_modes.hip
+read = ctx.lib.ta_debug_trace_read_split if prec in ('f16x3', 'f16x2') else ctx.lib.ta_debug_trace_read_split_modes
+read.argtypes = [C.c_void_p, C.c_int]
+assert read(buf, 16) == 0
 t = list(buf)
 base = min(t[0], t[8])
 names = {0: 'consumer entry', 1: 'consumer set up (waits B_0)', 2: 'slab 0 landed', 3: 'main loop done', 4: 'epilogue issued',
@@ -40,4 +42,4 @@ names = {0: 'consumer entry', 1: 'consumer set up (waits B_0)', 2: 'slab 0 lande
          8: 'producer entry', 9: 'producer addresses ready', 10: 'first slabs issued'}
 for i in (8, 9, 10, 0, 1, 2, 3, 5, 6, 7, 4):
     print('%-32s +%7d cycles' % (names[i], t[i] - base))
-print('layer k%d %d->%d @%dx%dx%d %s, stamped workgroup %s: %s' % (k, cin, cout, n, h, w, prec, int(os.environ.get('TA_CONV_PROBE', '0')) >> 8, ctx.conv_counts()))
+print('layer k%d %d->%d @%dx%dx%d %s, stamped workgroup %s: %s' % (k, cin, cout, n, h, w, prec, int(os.environ.get('TA_CONV_TRACE_BLOCK', '0')), ctx.conv_counts()))

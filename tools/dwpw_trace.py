@@ -31,8 +31,8 @@ for _ in range(3):
     m.forward_frames(fr)
 ctx.sync()
 buf = (C.c_longlong * 32)()
-ctx.lib.ta_debug_trace_read.argtypes = [C.c_void_p, C.c_int]
-assert ctx.lib.ta_debug_trace_read(buf, 32) == 0
+ctx.lib.ta_debug_trace_read_dwpw.argtypes = [C.c_void_p, C.c_int]       # the dw + pw unit's stamps (conv_dwpw.hip)
+assert ctx.lib.ta_debug_trace_read_dwpw(buf, 32) == 0
 t = list(buf)
 names = {16: 'entry', 17: 'pixel addresses ready', 18: 'slab 0 produced (taps loaded, rows written)', 19: 'past the first barrier (weights landed)',
          20: 'MFMAs issued', 21: 'finish: ring free', 22: 'tile parked', 23: 'drained (stores issued)'}

@@ -1,5 +1,5 @@
 """Register / LDS / spill figures of every kernel of a hipcc object file (the gfx950 code object inside its .hip_fatbin section):
-    python tools/kernel_resources.py terran_amd/csrc/conv_igemm.o [name filter]"""
+    python tools/kernel_resources.py terran_amd/csrc/conv_split.o [name filter]"""
 import re
 import struct
 import subprocess

@@ -6,9 +6,6 @@ cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
 ab() { echo "## $1   vs   $2"; bash tools/exp_ab.sh "$1" "$2" 3; }
 ab "--precision f16x3" "--precision f16x2"
-ab "TA_CONV_NO_WIN=1" "TA_CONV_NO_WIN="
-ab "TA_CONV_NO_W2=1" "TA_CONV_NO_W2="
-ab "TA_CONV_NO_FASTDRAIN=1" "TA_CONV_NO_FASTDRAIN="
 ab "--inflight 2" "--inflight 4"
 ab "--embed-min-crops 128 --embed-max-crops 192" "--embed-min-crops 320 --embed-max-crops 512"
 ab "--precision f32" "--precision bf16"
