@@ -108,20 +108,32 @@ int ta_frames_paste(ta_ctx* ctx, const ta_frames* src, int src_index, ta_frames*
  *                 drawn), a wider one the quadrilateral Pillow builds around the segment (coincident end points: one pixel).
  *   TA_DRAW_DISC  draw.ellipse([x0, y0, x1, y1], fill=): the filled ellipse in that box (x1 >= x0, y1 >= y0; the
  *                 box's width and height at most 32768).
+ *   TA_DRAW_MASK  draw.text's bitmap (ta_frames_draw_masks only): an 8-bit coverage bitmap whose top-left pixel lies at
+ *                 (x0, y0) and whose bottom-right one at (x1, y1), blended per pixel as DIV255(in * (255 - m) + ink * m)
+ *                 with the primitive's rgb; alpha must be 255.  A pixel whose coverage is 0 is left untouched.
  * Coordinates are pixels (what Pillow's int() of the float coordinates gives), |coordinate| <= 2^24.  The call runs on
  * `ctx`'s stream (a batch of another context on the same device may be drawn into) and returns when the drawing is done.
  * TA_E_INVALID: frame index out of range, unknown kind, inverted box, negative width, coordinate out of range. */
 #define TA_DRAW_BAR 0
 #define TA_DRAW_LINE 1
 #define TA_DRAW_DISC 2
+#define TA_DRAW_MASK 3
 typedef struct ta_draw_prim {
   int32_t frame;       /* image index in the batch                  */
   int32_t kind;        /* TA_DRAW_*                                 */
   int32_t x0, y0, x1, y1;
-  int32_t width;       /* TA_DRAW_LINE only                         */
+  int32_t width;       /* TA_DRAW_LINE: width; TA_DRAW_MASK: byte offset of the bitmap in `masks` */
   uint8_t rgba[4];     /* ink and alpha                             */
 } ta_draw_prim;
 int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n);
+/* ta_frames_draw with TA_DRAW_MASK primitives among the others.  `masks` is a host buffer of `mask_bytes` bytes that holds
+ * the coverage bitmaps: a mask primitive's `width` is the byte offset of its first row, rows are packed (pitch
+ * x1 - x0 + 1).  Any number of primitives, of any frames, may name the same bitmap.  The buffer travels to the device in
+ * the staging copy of the primitives.  TA_E_INVALID, before anything is drawn: what ta_frames_draw refuses, a mask
+ * primitive of alpha other than 255, a negative offset, a bitmap that reaches past `mask_bytes`, `masks` NULL with a mask
+ * primitive present.  (ta_frames_draw itself takes no masks: TA_DRAW_MASK is an unknown kind there.) */
+int ta_frames_draw_masks(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, const uint8_t* masks,
+                         size_t mask_bytes);
 
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's

@@ -1,9 +1,11 @@
-// ta_frames_draw: Pillow's ImageDraw.Draw(img, 'RGBA') primitives (terran/vis/pillow.py: rectangle outlines, wide and thin
-// lines, filled ellipses) rasterised into a resident frame batch in place, bit for bit.
+// ta_frames_draw / ta_frames_draw_masks: Pillow's ImageDraw.Draw(img, 'RGBA') primitives (terran/vis/pillow.py: rectangle
+// outlines and fills, wide and thin lines, filled ellipses, draw.text's coverage bitmaps) rasterised into a resident frame
+// batch in place, bit for bit.
 //
 // Host side (this file, C++): validation, a stable sort of the primitives by frame, the quadrilateral of every wide line
 // (Pillow's ImagingDrawWideLine: libm hypot and double rounding, done here so the device never re-derives a vertex) and
-// one span table per distinct ellipse box (Pillow's integer ellipse walk; a handful of shapes per call).
+// one span table per distinct ellipse box (Pillow's integer ellipse walk; a handful of shapes per call).  The coverage
+// bitmaps of mask primitives (rasterised by the caller: FreeType is host code) ride in the same staging copy.
 // Device side: one wave per frame row.  Every wave walks its frame's primitives in list order; for a primitive that covers
 // its row it computes the row's spans (uniform over the wave) and lane l blends the pixels x with x % 64 == l.  A pixel is
 // only ever read and written by one lane, in primitive order: the result does not depend on the launch geometry, and no
@@ -21,12 +23,13 @@
 
 namespace {
 
-enum { K_BAR = 0, K_THIN = 1, K_QUAD = 2, K_DISC = 3 };
+enum { K_BAR = 0, K_THIN = 1, K_QUAD = 2, K_DISC = 3, K_MASK = 4 };
 
 struct draw_rec {          // 64 bytes
   int32_t kind;
   uint32_t rgba;           // r | g << 8 | b << 16 | a << 24
   int32_t v[8];            // BAR: x0, x1 | THIN: x0, y0, x1, y1 | QUAD: vertices (x, y) x 4 | DISC: x0, y0, table offset
+                           // MASK: x0, x1, y0, byte offset of the bitmap (its pitch is x1 - x0 + 1)
   float dx[4];             // QUAD: edge i runs v[i] -> v[i + 1]; slope (x1 - x0) / (y1 - y0) as Pillow's add_edge computes it
   int32_t pymax;           // QUAD: the scan's last row as Pillow clamps it (min(H, max(0, ymax)))
   int32_t pad[1];
@@ -185,7 +188,8 @@ __device__ inline bool thin_row(const draw_rec& r, int y, int& lo_x, int& hi_x) 
 
 __global__ __launch_bounds__(256) void draw_kernel(uint8_t* __restrict__ frames, int H, int W,
                                                    const int32_t* __restrict__ fstart, const int2* __restrict__ ybound,
-                                                   const draw_rec* __restrict__ recs, const int2* __restrict__ disc_tab) {
+                                                   const draw_rec* __restrict__ recs, const int2* __restrict__ disc_tab,
+                                                   const uint8_t* __restrict__ masks) {
   const int f = blockIdx.y;
   const int y = blockIdx.x * 4 + (int)(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -218,6 +222,22 @@ __global__ __launch_bounds__(256) void draw_kernel(uint8_t* __restrict__ frames,
       if (thin_row(r, y, lo, hi)) blend(lo, hi);
     } else if (r.kind == K_QUAD) {
       quad_row(r, y, blend);
+    } else if (r.kind == K_MASK) {
+      // the bitmap's row is contiguous: the 64 lanes read 64 consecutive bytes; coverage m plays the alpha
+      const int x0 = r.v[0], lo = max(x0, 0), hi = min(r.v[1], W - 1);
+      const uint8_t* mrow = masks + (size_t)r.v[3] + (size_t)(y - r.v[2]) * (size_t)(r.v[1] - x0 + 1);
+      const int ir = (int)(r.rgba & 255), ig = (int)((r.rgba >> 8) & 255), ibl = (int)((r.rgba >> 16) & 255);
+      for (int x = (lo & ~63) + lane; x <= hi; x += 64) {
+        if (x < lo) continue;
+        const int m = mrow[x - x0];
+        if (m == 0) continue;
+        uint8_t* px = row + (size_t)x * 3;
+        const int vr = px[0] * (255 - m) + ir * m + 128, vg = px[1] * (255 - m) + ig * m + 128,
+                  vb = px[2] * (255 - m) + ibl * m + 128;
+        px[0] = (uint8_t)(((vr >> 8) + vr) >> 8);
+        px[1] = (uint8_t)(((vg >> 8) + vg) >> 8);
+        px[2] = (uint8_t)(((vb >> 8) + vb) >> 8);
+      }
     } else {
       const int2 t = disc_tab[r.v[2] + (y - r.v[1])];
       blend(r.v[0] + t.x, r.v[0] + t.y);
@@ -311,11 +331,9 @@ void disc_rows(int a, int b, std::vector<int2>& tab) {
   }
 }
 
-}  // namespace
-
-extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n) {
-  ta_enter(ctx);
-  if (!ctx) return TA_E_INVALID;
+// both entry points; `with_masks`: TA_DRAW_MASK is a known kind and `masks` (mask_bytes bytes, may be NULL) holds the bitmaps
+int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool with_masks, const uint8_t* masks,
+         size_t mask_bytes) {
   if (!frames || n < 0 || (n > 0 && !prims)) return ta_fail(ctx, TA_E_INVALID, "frames_draw: bad args");
   if (frames->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_draw: the batch lives on another device");
   const int N = frames->n, H = frames->h, W = frames->w;
@@ -323,7 +341,7 @@ extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim
   for (int i = 0; i < n; ++i) {
     const ta_draw_prim& q = prims[i];
     if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: frame %d out of range [0, %d)", i, q.frame, N);
-    if (q.kind != TA_DRAW_BAR && q.kind != TA_DRAW_LINE && q.kind != TA_DRAW_DISC)
+    if (q.kind != TA_DRAW_BAR && q.kind != TA_DRAW_LINE && q.kind != TA_DRAW_DISC && !(with_masks && q.kind == TA_DRAW_MASK))
       return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: unknown kind %d", i, q.kind);
     if (std::abs((int64_t)q.x0) > LIM || std::abs((int64_t)q.y0) > LIM || std::abs((int64_t)q.x1) > LIM || std::abs((int64_t)q.y1) > LIM)
       return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: coordinate beyond +-2^24", i);
@@ -332,6 +350,15 @@ extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim
     if (q.kind == TA_DRAW_DISC && (q.x1 - q.x0 > 32768 || q.y1 - q.y0 > 32768))
       return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: ellipse box larger than 32768", i);
     if (q.kind == TA_DRAW_LINE && q.width < 0) return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: negative width", i);
+    if (q.kind == TA_DRAW_MASK) {
+      if (q.rgba[3] != 255) return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: a mask's alpha must be 255", i);
+      if (!masks) return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: a mask primitive, but no masks", i);
+      if (q.width < 0) return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: negative mask offset", i);
+      const uint64_t end = (uint64_t)q.width + (uint64_t)(q.x1 - q.x0 + 1) * (uint64_t)(q.y1 - q.y0 + 1);   // < 2^52
+      if (end > (uint64_t)mask_bytes)
+        return ta_fail(ctx, TA_E_INVALID, "frames_draw: primitive %d: mask reaches byte %llu of %llu", i, (unsigned long long)end,
+                       (unsigned long long)mask_bytes);
+    }
   }
   if (n == 0 || N == 0 || H == 0 || W == 0) return TA_OK;
 
@@ -356,6 +383,15 @@ extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim
       r.kind = K_BAR;
       r.v[0] = q.x0;
       r.v[1] = q.x1;
+      ylo = q.y0;
+      yhi = q.y1;
+      if (q.x1 < 0 || q.x0 >= W) ylo = 1, yhi = 0;
+    } else if (q.kind == TA_DRAW_MASK) {
+      r.kind = K_MASK;
+      r.v[0] = q.x0;
+      r.v[1] = q.x1;
+      r.v[2] = q.y0;
+      r.v[3] = q.width;
       ylo = q.y0;
       yhi = q.y1;
       if (q.x1 < 0 || q.x0 >= W) ylo = 1, yhi = 0;
@@ -412,7 +448,8 @@ extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim
   const size_t b_fs = fstart.size() * sizeof(int32_t), b_yb = (size_t)n * sizeof(int2), b_rec = (size_t)n * sizeof(draw_rec),
                b_tab = tab.size() * sizeof(int2);
   const size_t o_yb = (b_fs + 15) & ~(size_t)15, o_rec = (o_yb + b_yb + 63) & ~(size_t)63, o_tab = o_rec + b_rec;
-  const size_t total = o_tab + b_tab;
+  const size_t o_mask = o_tab + b_tab, b_mask = masks ? mask_bytes : 0;
+  const size_t total = o_mask + b_mask;
   void *scr = nullptr, *pin = nullptr;
   TA_TRY(ta_scratch(ctx, total, &scr));
   TA_TRY(ta_pinned(ctx, total, &pin));
@@ -421,11 +458,28 @@ extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim
   memcpy(hp + o_yb, yb.data(), b_yb);
   memcpy(hp + o_rec, recs.data(), b_rec);
   memcpy(hp + o_tab, tab.data(), b_tab);
+  if (b_mask) memcpy(hp + o_mask, masks, b_mask);
   TA_HIP(ctx, hipMemcpyAsync(scr, pin, total, hipMemcpyHostToDevice, ctx->stream));
   char* dp = (char*)scr;
   hipLaunchKernelGGL(draw_kernel, dim3((H + 3) / 4, N), dim3(256), 0, ctx->stream, frames->dev, H, W, (const int32_t*)dp,
-                     (const int2*)(dp + o_yb), (const draw_rec*)(dp + o_rec), (const int2*)(dp + o_tab));
+                     (const int2*)(dp + o_yb), (const draw_rec*)(dp + o_rec), (const int2*)(dp + o_tab),
+                     (const uint8_t*)(dp + o_mask));
   TA_HIP(ctx, hipGetLastError());
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call
   return TA_OK;
+}
+
+}  // namespace
+
+extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n) {
+  ta_enter(ctx);
+  if (!ctx) return TA_E_INVALID;
+  return draw(ctx, frames, prims, n, false, nullptr, 0);
+}
+
+extern "C" int ta_frames_draw_masks(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, const uint8_t* masks,
+                                    size_t mask_bytes) {
+  ta_enter(ctx);
+  if (!ctx) return TA_E_INVALID;
+  return draw(ctx, frames, prims, n, true, masks, mask_bytes);
 }

@@ -51,6 +51,7 @@ SIGNATURES = {
     'ta_frames_resize_bicubic': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p)]),
     'ta_frames_paste': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
     'ta_frames_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'ta_frames_draw_masks': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -91,7 +92,7 @@ SIGNATURES = {
 }
 
 # ta_draw_prim (include/terran_amd.h) and its kinds TA_DRAW_*
-DRAW_BAR, DRAW_LINE, DRAW_DISC = 0, 1, 2
+DRAW_BAR, DRAW_LINE, DRAW_DISC, DRAW_MASK = 0, 1, 2, 3
 PRIM_DT = np.dtype([('frame', '<i4'), ('kind', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'),
                     ('width', '<i4'), ('rgba', 'u1', (4,))])
 assert PRIM_DT.itemsize == 32
@@ -433,12 +434,19 @@ class Frames:
     def paste(self, src, src_index, dst_index, top, left):
         self.ctx.check(self.ctx.lib.ta_frames_paste(self.ctx.h, src.h, src_index, self.h, dst_index, top, left))
 
-    def draw(self, prims, ctx=None):
-        """Draw `prims` (a PRIM_DT array, in order) into this batch in place (ta_frames_draw).  `ctx`: the context the
-        drawing runs on -- the CALLER's, as in `resize`."""
+    def draw(self, prims, masks=None, ctx=None):
+        """Draw `prims` (a PRIM_DT array, in order) into this batch in place (ta_frames_draw).  `masks`: the uint8 buffer
+        that holds the coverage bitmaps of the DRAW_MASK primitives, each at the byte offset its `width` names
+        (ta_frames_draw_masks); without it a DRAW_MASK primitive is an unknown kind.  `ctx`: the context the drawing runs
+        on -- the CALLER's, as in `resize`."""
         ctx = ctx or self.ctx
         prims = np.ascontiguousarray(prims, dtype=PRIM_DT)
-        ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, ptr(prims) if len(prims) else None, len(prims)))
+        pp = ptr(prims) if len(prims) else None
+        if masks is None:
+            ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, pp, len(prims)))
+            return
+        masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+        ctx.check(ctx.lib.ta_frames_draw_masks(ctx.h, self.h, pp, len(prims), ptr(masks) if len(masks) else None, len(masks)))
 
     def encode_jpeg(self, quality=75, subsampling=2, ctx=None):
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs

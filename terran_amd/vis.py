@@ -10,12 +10,18 @@ restated in csrc/draw.hip).  The colours follow the reference's tables; FACE_COL
 stateful: a label gets the next palette colour the first time it is seen, and a face without a label (no `name`, and
 `track` absent or 0) a random one from Python's `random`.
 
-Known difference: faces that carry `text` or `track` get their marker in the label's colour, but the label text itself is
-not rendered (the reference's `draw_label` raises AttributeError on Pillow >= 10, so it renders none either).
+Labels (`labels=True` on vis_faces / draw_faces / pack_faces; off by default): a face that carries `text`, or else
+`track` (label '#<track>'), gets the reference's `draw_label` after its marker -- a filled tab in the face's colour at the
+box's top-left corner and the text on it in white -- with `FreeTypeFont.getsize(t)`, which Pillow 10 removed and the
+reference still calls, read as `getbbox(t)[2:4]` (what it returned).  The glyphs are rasterised on the host by Pillow's
+font (FreeType), once per distinct (font, size, text, fractional start): an LRU keeps the coverage bitmaps, and a call
+uploads each distinct one once, however many frames show it.  The tab is a bar, the text a DRAW_MASK primitive.
 
-Host glue only: the packing of results into primitives is vectorised numpy; the drawing is one ta_frames_draw launch.
-Importing this module needs no GPU.
+Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch.
+Importing this module needs no GPU and no Pillow.
 """
+import collections
+import math
 import random
 
 import numpy as np
@@ -74,18 +80,162 @@ def _check_coords(a, what):
         raise ValueError('%s coordinates must be finite and within +-2^24' % what)
 
 
-def pack_faces(faces_per_frame, scale=1.0):
+# ---- labels: the reference's draw_label --------------------------------------------------------------------------------
+LABEL_FONT_NAMES = ('DejaVuSans-Bold', 'DroidSans-Bold')        # the reference's choice on Linux, in its order
+LABEL_CACHE_SIZE = 1024
+LABEL_INK = (255, 255, 255, 255)                                # draw.text's default ink
+
+
+class PillowFont:
+    """What label packing needs of a font: `key` (hashable: which font, which size), `measure(text)` -> (width, height),
+    the reference's `getsize`, and `mask(text, start)` -> (uint8 (h, w) coverage bitmap, (x, y) offset from the integer
+    pen position), what draw.text places.  This one wraps a Pillow font, FreeType or bitmap."""
+
+    def __init__(self, font, key):
+        self.font, self.key = font, key
+
+    def measure(self, text):
+        return tuple(self.font.getbbox(text)[2:4])
+
+    def mask(self, text, start):
+        try:
+            core, offset = self.font.getmask2(text, 'L', anchor='la', start=start)
+        except AttributeError:                          # a bitmap font: no bearings, no fractional start
+            core, offset = self.font.getmask(text, 'L'), (0, 0)
+        w, h = core.size
+        bitmap = np.frombuffer(bytes(core), np.uint8).reshape(h, w) if w and h else np.zeros((0, 0), np.uint8)
+        return bitmap, (int(offset[0]), int(offset[1]))
+
+
+_system_font = []                                       # [font or None], resolved on first use
+_fonts = {}                                             # size -> PillowFont
+_masks = collections.OrderedDict()    # (font key, text, start) -> (bitmap, offset), (font key, text, None) -> metrics: an LRU
+
+
+def label_font(size):
+    """The reference's label font at `size` (its round(16 * scale)): DejaVuSans-Bold as ImageFont.truetype finds it,
+    else Pillow's default font as it is."""
+    if size not in _fonts:
+        from PIL import ImageFont
+        if not _system_font:
+            font = None
+            for name in LABEL_FONT_NAMES:
+                try:
+                    font = ImageFont.truetype(name)
+                    break
+                except IOError:
+                    continue
+            _system_font.append(font)
+        base = _system_font[0]
+        if base is not None:
+            _fonts[size] = PillowFont(base.font_variant(size=size), (base.path, size))
+        else:
+            _fonts[size] = PillowFont(ImageFont.load_default(), ('default', 0))
+    return _fonts[size]
+
+
+def _cached(key, make):
+    hit = _masks.get(key)
+    if hit is None:
+        hit = _masks[key] = make()
+        while len(_masks) > LABEL_CACHE_SIZE:
+            _masks.popitem(last=False)
+    else:
+        _masks.move_to_end(key)
+    return hit
+
+
+def _label_measure(font, text):
+    return _cached((font.key, text, None), lambda: font.measure(text))
+
+
+def _label_mask(font, text, start):
+    def make():
+        bitmap, offset = font.mask(text, start)
+        return bitmap if bitmap.any() else bitmap[:0], offset      # no coverage (spaces): nothing to place
+    key = (font.key, text, start)
+    return key, _cached(key, make)
+
+
+def _face_text(face):
+    if face.get('text') is not None:
+        return str(face['text'])
+    if face.get('track') is not None:
+        return '#%s' % (face['track'],)
+    return None
+
+
+def _pack_labels(labelled, colors, frame, scale):
+    """draw_label for the faces `labelled` [(face index, bbox as the caller gave it, text)] -> (PRIM_DT array of a tab and
+    a mask per label, face index of each, atlas).  The corner arithmetic runs on the caller's own scalars, as the
+    reference's does (a float32 box stays float32 under NumPy 2), and is then converted as Pillow converts it: float(),
+    C's (int) for the rectangle, int() and math.modf for the text."""
+    size = round(16 * scale)
+    if size < 1:
+        raise ValueError('font size must be greater than 0, not %d (scale %r)' % (size, scale))
+    for _, _, text in labelled:
+        if '\n' in text:
+            raise ValueError('multiline labels are not supported: %r' % text)
+    font = label_font(size)
+    margin_w = 0.2 * _label_measure(font, 'M')[0]
+    line_h = _label_measure(font, 'Mq')[1]
+    atlas, where, total = [], {}, 0
+    rows = []                                           # (face, frame, kind, x0, y0, x1, y1, width, r, g, b)
+    for i, bbox, text in labelled:
+        x, y = bbox[0], bbox[1]
+        x1, y1 = int(float(x + _label_measure(font, text)[0] + 3 * margin_w)), int(float(y + line_h * 1.15))
+        rows.append((i, frame[i], lib.DRAW_BAR, int(float(x)), int(float(y)), min(x1, COORD_LIMIT), min(y1, COORD_LIMIT), 0)
+                    + tuple(colors[i]))
+        tx, ty = float(x + margin_w), float(y)
+        key, (bitmap, offset) = _label_mask(font, text, (math.modf(tx)[0], math.modf(ty)[0]))
+        h, w = bitmap.shape
+        x0, y0 = int(tx) + offset[0], int(ty) + offset[1]
+        if not bitmap.size or max(abs(x0), abs(y0), abs(x0 + w - 1), abs(y0 + h - 1)) > COORD_LIMIT:
+            continue                                    # a label of spaces: the tab only; beyond any frame: nothing to see
+        if key not in where:
+            where[key] = total
+            atlas.append(bitmap.ravel())
+            total += bitmap.size
+        rows.append((i, frame[i], lib.DRAW_MASK, x0, y0, x0 + w - 1, y0 + h - 1, where[key]) + LABEL_INK[:3])
+    r = np.array(rows, np.int64)
+    out = _prims(len(r))
+    for c, name in enumerate(('frame', 'kind', 'x0', 'y0', 'x1', 'y1', 'width'), 1):
+        out[name] = r[:, c]
+    out['rgba'][:, :3] = r[:, 8:]
+    out['rgba'][:, 3] = MARKER_ALPHA
+    return out, r[:, 0], np.concatenate(atlas) if atlas else np.zeros(0, np.uint8)
+
+
+def pack_faces(faces_per_frame, scale=1.0, labels=False):
     """-> PRIM_DT array: each face's rectangle outline (Pillow draw.rectangle(bbox, outline=rgb + (255,), width=int(3 *
     scale))) as up to four opaque bars, faces in order, frame by frame.  Every box is checked first: an inverted one
-    raises ValueError (as Pillow does) before anything is drawn."""
-    boxes, colors, frame = [], [], []
+    raises ValueError (as Pillow does) before anything is drawn.
+
+    labels=True -> (PRIM_DT array, uint8 atlas): after its marker every face with `text` or `track` gets its label, a
+    bar (the tab) and a DRAW_MASK primitive (the text) whose `width` is the offset of its bitmap in the atlas; equal
+    bitmaps share one place there.  `Frames.draw(prims, masks=atlas)` draws them."""
+    boxes, colors, frame, labelled = [], [], [], []
     for f, faces in enumerate(faces_per_frame):
         for face in _as_list(faces):
             colors.append(FACE_COLORMAP(face.get('name') or face.get('track')))
             boxes.append(np.asarray(face['bbox'], np.float64).reshape(4))
             frame.append(f)
+            if labels and _face_text(face) is not None:
+                labelled.append((len(boxes) - 1, face['bbox'], _face_text(face)))
+    prims, face_of = _pack_markers(boxes, colors, frame, scale)
+    if not labels:
+        return prims
+    if not labelled:
+        return prims, np.zeros(0, np.uint8)
+    tabs, tab_face, atlas = _pack_labels(labelled, colors, frame, scale)
+    both, face_of = np.concatenate([prims, tabs]), np.concatenate([face_of, tab_face])
+    return both[np.argsort(face_of, kind='stable')], atlas     # face by face: marker, tab, text
+
+
+def _pack_markers(boxes, colors, frame, scale):
+    """-> (PRIM_DT array of the faces' outlines, face index of each bar)."""
     if not boxes:
-        return _prims(0)
+        return _prims(0), np.zeros(0, np.int64)
     b = np.stack(boxes)
     if np.any(b[:, 2] < b[:, 0]):
         raise ValueError('x1 must be greater than or equal to x0')
@@ -94,7 +244,7 @@ def pack_faces(faces_per_frame, scale=1.0):
     _check_coords(b, 'box')
     w = int(3 * scale)
     if w <= 0:                                          # Pillow: rectangle(width=0) draws nothing
-        return _prims(0)
+        return _prims(0), np.zeros(0, np.int64)
     x0, y0, x1, y1 = np.trunc(b).astype(np.int64).T     # Pillow's (int) of the float coordinates
     # outline of width w: rows y0 .. y0+w-1 and y1-w+1 .. y1 across x0..x1, and the columns x0 .. x0+w-1, x1-w+1 .. x1
     # over the rows of Pillow's side lines from y0+w towards y1-w+1 (its end point excluded)
@@ -111,7 +261,8 @@ def pack_faces(faces_per_frame, scale=1.0):
     out['y1'] = np.stack([y0 + w - 1, y1, s_hi, s_hi], 1).ravel()
     out['rgba'][:, :3] = np.repeat(np.array(colors, np.uint8), 4, 0)
     out['rgba'][:, 3] = MARKER_ALPHA
-    return out[(out['y1'] >= out['y0']) & (out['x1'] >= out['x0'])]
+    keep = (out['y1'] >= out['y0']) & (out['x1'] >= out['x0'])
+    return out[keep], np.repeat(np.arange(m), 4)[keep]
 
 
 def _keypoints(poses_per_frame):
@@ -166,12 +317,15 @@ def _check_batch(frames, per_frame):
         raise ValueError('%d result lists for a batch of %d frames' % (len(per_frame), len(frames)))
 
 
-def draw_faces(frames, faces_per_frame, scale=1.0, ctx=None):
+def draw_faces(frames, faces_per_frame, scale=1.0, ctx=None, labels=False):
     """Draw face markers into the resident batch `frames` (lib.Frames) in place: faces_per_frame[i] (a dict, or a list of
     dicts as face_detection / face_tracking return) goes into frame i.  `ctx`: the caller's context (default: the
-    batch's own)."""
+    batch's own).  `labels`: write each face's `text`, or '#<track>', on a tab at its box's corner."""
     _check_batch(frames, faces_per_frame)
-    frames.draw(pack_faces(faces_per_frame, scale), ctx=ctx)
+    if labels:
+        frames.draw(*pack_faces(faces_per_frame, scale, labels=True), ctx=ctx)
+    else:
+        frames.draw(pack_faces(faces_per_frame, scale), ctx=ctx)
     return frames
 
 
@@ -182,7 +336,7 @@ def draw_poses(frames, poses_per_frame, scale=1.0, ctx=None):
     return frames
 
 
-def _on_host_image(image, prims, device=None):
+def _on_host_image(image, prims, masks=None, device=None):
     from . import runtime
     image = np.asarray(image)
     if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
@@ -190,14 +344,17 @@ def _on_host_image(image, prims, device=None):
     ctx = runtime.get_context(device)
     frames = ctx.upload(image[None])
     try:
-        frames.draw(prims)
+        frames.draw(prims, masks)
         return frames.download()[0]
     finally:
         frames.free()
 
 
-def vis_faces(image, faces, scale=1.0):
-    """terran.vis.vis_faces: a copy of `image` with a box drawn over every face (dict or list of dicts)."""
+def vis_faces(image, faces, scale=1.0, labels=False):
+    """terran.vis.vis_faces: a copy of `image` with a box drawn over every face (dict or list of dicts), and with
+    `labels` the face's `text`, or '#<track>', on a tab at the box's corner."""
+    if labels:
+        return _on_host_image(image, *pack_faces([faces], scale, labels=True))
     return _on_host_image(image, pack_faces([faces], scale))
 
 
