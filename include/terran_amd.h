@@ -191,8 +191,8 @@ int ta_jpeg_last_stats(const ta_ctx* ctx, double* ms, int64_t* counts);
 /* ---- JPEG encode (Image.fromarray(frame).save(f, 'JPEG', quality=q, subsampling=s) with Pillow's other defaults) ---- */
 /* Baseline JFIF files byte for byte as Pillow / libjpeg-turbo writes them: Annex K quantisation tables scaled by
  * `quality` (1..100, force_baseline), islow forward DCT, standard Huffman tables, no restart markers, no smoothing.
- * subsampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's default).  Progressive, optimized Huffman tables, custom
- * quantisation tables, restart intervals and metadata segments are not offered. */
+ * subsampling: 0 = 4:4:4, 1 = 4:2:2, 2 = 4:2:0 (Pillow's default).  Optimized Huffman tables: ta_jpeg_encode_opt.
+ * Progressive, custom quantisation tables, restart intervals and metadata segments are not offered. */
 /* HOST ONLY, no context: the header Pillow writes for an h x w RGB image (SOI .. SOS).  *size gets its length; capacity
  * < *size gives TA_E_CAPACITY.  Bad arguments: TA_E_INVALID. */
 int ta_jpeg_encode_header(int h, int w, int quality, int subsampling, uint8_t* out, size_t capacity, size_t* size);
@@ -207,6 +207,23 @@ int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality, int subsam
  * pack), the device-to-host copy of the files; then the host wall time of the whole call.  counts[4]: images, blocks,
  * bytes copied to the host, entropy-coded bytes before stuffing. */
 int ta_jpeg_encode_last_stats(const ta_ctx* ctx, double* ms, int64_t* counts);
+/* ta_jpeg_encode with Pillow's `optimize` option.  optimize = 0 is ta_jpeg_encode itself (the standard Huffman tables,
+ * the same launches, the same bytes).  optimize = 1 writes what save(..., optimize=True) writes: every image is coded
+ * with tables built from its own symbol statistics (libjpeg's jpeg_gen_optimal_table; Cb and Cr share table 1), which
+ * its header carries in four DHT segments.  One more device pass counts the symbols and the histograms (2 176 bytes an
+ * image) visit the host, which builds the tables.  An image of 10^9 / 64 blocks or more is refused (TA_E_INVALID,
+ * before any launch): libjpeg's frequency arithmetic assumes counts below 10^9. */
+int ta_jpeg_encode_opt(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, int optimize,
+                       const uint8_t** out, size_t* sizes);
+/* HOST ONLY, no context: libjpeg's optimal Huffman table for the symbol frequencies freq[0..255] (each 0 .. 10^9 - 1,
+ * at least one nonzero; freq[256], the reserved pseudo-symbol that keeps the all-ones code free, is taken as 1 whatever
+ * it holds).  bits[1..16] get the number of codes of each length (bits[0] = 0), vals[0 .. *nvals) the symbols in code
+ * order.  Bad arguments: TA_E_INVALID. */
+int ta_jpeg_optimal_table(const int64_t* freq, uint8_t* bits, uint8_t* vals, int* nvals);
+/* More figures of the last ta_jpeg_encode_opt on this context (zeros after an optimize = 0 call).  ms[2]: HIP-event
+ * time of the statistics pass (0 unless ta_profile_enable is on; its histogram copy and synchronisation are not in it),
+ * host wall time of building the tables and headers. */
+int ta_jpeg_encode_last_opt_stats(const ta_ctx* ctx, double* ms);
 
 /* ---- models ---------------------------------------------------------------------------- */
 /* `blob` is the packed model produced by terran_amd/pack.py from a Terran state_dict

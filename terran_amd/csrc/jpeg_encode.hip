@@ -21,6 +21,14 @@
 //   S  je_scan_kernel   per image: chunk offsets of the stuffing zeros, the image's total; to the host again
 //   E4b je_pack_kernel  header, stuffed stream and EOI of every image, back to back, into one packed buffer
 // then ONE device-to-host copy of the packed files into the context's pinned output.
+//
+// optimize = 1 (Pillow's optimize=True: per-image Huffman tables) adds, between E1 and E2,
+//   ES je_stat_kernel   symbol counts of every image per table class (0: Y, 1: Cb and Cr): DC categories, AC
+//                       (run << 4) | size, ZRL, EOB -- the symbols E2 / E3 code, from the same walk_block
+// whose histograms (JE_TABLE_WORDS uint32 an image) go to the host.  It builds every table as libjpeg's
+// jpeg_gen_optimal_table does (optimal_table below), the code words E2 / E3 read (one table set per image) and every
+// image's own header (its DHT segments differ in length), and sends both back.  With optimize = 0 E2 / E3 read the one
+// standard table set (stride 0) and every image's header entry names the one shared header.
 #include <string.h>
 
 #include <chrono>
@@ -33,6 +41,9 @@ namespace {
 #define JE_SLOTS 256                     // slots per chunk (= E2 / E3 workgroup)
 #define JE_FF_CHUNK 4096                 // stream bytes per E4 workgroup: 256 threads x 16 bytes
 #define JE_LDS_STRIDE 72                 // ints per block in LDS (E1), as in the decoder's IDCT kernel
+#define JE_TABLE_WORDS 544               // one table set: dc [2][16], ac [2][256]; code words and histograms alike
+#define JE_HEADER_STRIDE 1024            // room for one optimized header (at most 191 + 2 x (37 + 277) bytes)
+#define JE_MAX_COUNT 1000000000ll        // jpeg_gen_optimal_table's "infinite" frequency
 
 struct je_params {
   const uint8_t* src;                    // (n, h, w, 3) uint8
@@ -117,8 +128,15 @@ void put_segment(std::vector<uint8_t>& o, uint8_t marker, const std::vector<uint
   o.insert(o.end(), payload.begin(), payload.end());
 }
 
-// SOI .. SOS as libjpeg-turbo writes them for Pillow's defaults
-std::vector<uint8_t> make_header(int h, int w, int quality, int subsampling) {
+struct je_huff {                         // one table as a DHT segment holds it
+  uint8_t bits[17];                      // [1..16]: codes of each length
+  uint8_t vals[256];
+  int nvals;
+};
+
+// SOI .. SOS as libjpeg-turbo writes them for Pillow's defaults; opt: the image's own tables (DC 0, AC 0, DC 1, AC 1)
+// in place of the standard ones
+std::vector<uint8_t> make_header(int h, int w, int quality, int subsampling, const je_huff* opt = nullptr) {
   std::vector<uint8_t> o = {0xFF, 0xD8};
   put_segment(o, 0xE0, {'J', 'F', 'I', 'F', 0, 1, 1, 0, 0, 1, 0, 1, 0, 0});
   for (int t = 0; t < 2; ++t) {
@@ -139,14 +157,81 @@ std::vector<uint8_t> make_header(int h, int w, int quality, int subsampling) {
               {0x10, kAcLumaBits, kAcLumaVals, 162},
               {0x01, kDcChromaBits, kDcVals, 12},
               {0x11, kAcChromaBits, kAcChromaVals, 162}};
-  for (const auto& d : dht) {
+  for (int k = 0; k < 4; ++k) {
+    const auto& d = dht[k];
     std::vector<uint8_t> p = {d.id};
-    p.insert(p.end(), d.bits, d.bits + 16);
-    p.insert(p.end(), d.vals, d.vals + d.nv);
+    if (opt) {
+      p.insert(p.end(), opt[k].bits + 1, opt[k].bits + 17);
+      p.insert(p.end(), opt[k].vals, opt[k].vals + opt[k].nvals);
+    } else {
+      p.insert(p.end(), d.bits, d.bits + 16);
+      p.insert(p.end(), d.vals, d.vals + d.nv);
+    }
     put_segment(o, 0xC4, p);
   }
   put_segment(o, 0xDA, {3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0});
   return o;
+}
+
+// jchuff.c jpeg_gen_optimal_table (Annex K.2 with libjpeg's choices, which Pillow's files show): freq[0..255] symbol
+// counts below JE_MAX_COUNT, not all zero; freq[256] is the pseudo-symbol that keeps the all-ones code free
+// false: a code longer than 32 bits (libjpeg's JERR_HUFF_CLEN_OVERFLOW)
+bool optimal_table(const int64_t* counts, je_huff* out) {
+  const int kMaxLen = 32;
+  int64_t freq[257];
+  int codesize[257], others[257];
+  uint8_t bits[kMaxLen + 1] = {};
+  for (int i = 0; i < 256; ++i) freq[i] = counts[i];
+  freq[256] = 1;
+  for (int i = 0; i < 257; ++i) {
+    codesize[i] = 0;
+    others[i] = -1;
+  }
+  for (;;) {
+    // the two least frequent entries; of equal ones the larger symbol first
+    int c1 = -1, c2 = -1;
+    int64_t v = JE_MAX_COUNT;
+    for (int i = 0; i <= 256; ++i)
+      if (freq[i] && freq[i] <= v) {
+        v = freq[i];
+        c1 = i;
+      }
+    v = JE_MAX_COUNT;
+    for (int i = 0; i <= 256; ++i)
+      if (freq[i] && freq[i] <= v && i != c1) {
+        v = freq[i];
+        c2 = i;
+      }
+    if (c2 < 0) break;
+    freq[c1] += freq[c2];
+    freq[c2] = 0;
+    for (++codesize[c1]; others[c1] >= 0;) ++codesize[c1 = others[c1]];
+    others[c1] = c2;
+    for (++codesize[c2]; others[c2] >= 0;) ++codesize[c2 = others[c2]];
+  }
+  for (int i = 0; i <= 256; ++i) {
+    if (codesize[i] > kMaxLen) return false;
+    if (codesize[i]) ++bits[codesize[i]];
+  }
+  int i = kMaxLen;
+  for (; i > 16; --i)                                          // no code longer than 16: shorten in pairs
+    while (bits[i] > 0) {
+      int j = i - 2;
+      while (bits[j] == 0) --j;
+      bits[i] -= 2;
+      ++bits[i - 1];
+      bits[j + 1] += 2;
+      --bits[j];
+    }
+  while (bits[i] == 0) --i;                                    // the pseudo-symbol leaves the longest length
+  --bits[i];
+  memcpy(out->bits, bits, 17);
+  int p = 0;
+  for (int len = 1; len <= kMaxLen; ++len)
+    for (int j = 0; j < 256; ++j)
+      if (codesize[j] == len) out->vals[p++] = (uint8_t)j;
+  out->nvals = p;
+  return true;
 }
 
 inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -329,10 +414,11 @@ __device__ __forceinline__ int pred_dc(const je_params& p, const int16_t* __rest
 
 __device__ __forceinline__ int category(int v) { return v ? 32 - __clz(abs(v)) : 0; }
 
-// Calls put(bits, length) for every code of the block (code and value bits joined: at most 16 + 11 bits)
+// The one walk E2, E3 and the statistics pass share: calls sym(ac, symbol, value bits, size) for every code of the
+// block -- ac 0: the DC table, symbol = size = the category of the difference to pred; ac 1: the AC table, symbol
+// (run << 4) | size, 0xF0 (ZRL) or 0x00 (EOB) with no value bits
 template <class F>
-__device__ __forceinline__ void walk_block(const int16_t* __restrict__ blk, int pred, const uint32_t* __restrict__ dct,
-                                           const uint32_t* __restrict__ act, F&& put) {
+__device__ __forceinline__ void walk_block(const int16_t* __restrict__ blk, int pred, F&& sym) {
   uint64_t nz = 0;
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -346,29 +432,32 @@ __device__ __forceinline__ void walk_block(const int16_t* __restrict__ blk, int 
   }
   const int diff = blk[0] - pred;
   int s = category(diff);
-  uint32_t e = dct[s];
-  put(((e & 0xFFFF) << s) | ((uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1)), (int)(e >> 16) + s);
+  sym(0, s, (uint32_t)(diff < 0 ? diff - 1 : diff) & ((1u << s) - 1), s);
   nz &= ~1ull;
   int last = 0;
-  const uint32_t zrl = act[0xF0];
   while (nz) {
     const int k = __ffsll((unsigned long long)nz) - 1;
     nz &= nz - 1;
     int run = k - last - 1;
-    for (; run > 15; run -= 16) put(zrl & 0xFFFF, (int)(zrl >> 16));
+    for (; run > 15; run -= 16) sym(1, 0xF0, 0u, 0);
     const int a = blk[k];
     s = category(a);
-    e = act[(run << 4) | s];
-    put(((e & 0xFFFF) << s) | ((uint32_t)(a < 0 ? a - 1 : a) & ((1u << s) - 1)), (int)(e >> 16) + s);
+    sym(1, (run << 4) | s, (uint32_t)(a < 0 ? a - 1 : a) & ((1u << s) - 1), s);
     last = k;
   }
-  if (last != 63) put(act[0] & 0xFFFF, (int)(act[0] >> 16));
+  if (last != 63) sym(1, 0x00, 0u, 0);
 }
 
-// tables: dc codes [2][16], ac codes [2][256] ((length << 16) | code)
+// where table class t (0: Y, 1: Cb / Cr) keeps symbol `symbol` in one table set (code words or histogram)
+__device__ __forceinline__ int table_word(int t, int ac, int symbol) {
+  return (ac ? 32 + 256 * t : 16 * t) + symbol;
+}
+
+// tables: dc codes [2][16], ac codes [2][256] ((length << 16) | code); image i reads the set at i * table_stride words
+// (0: one set for every image)
 __global__ void __launch_bounds__(256) je_len_kernel(je_params p, const int16_t* __restrict__ coefs,
-                                                     const uint32_t* __restrict__ tables, uint32_t* __restrict__ lens,
-                                                     uint32_t* __restrict__ chunk_tot) {
+                                                     const uint32_t* __restrict__ tables, int table_stride,
+                                                     uint32_t* __restrict__ lens, uint32_t* __restrict__ chunk_tot) {
   __shared__ uint32_t lds[4];
   const int64_t slot = (int64_t)blockIdx.x * JE_SLOTS + threadIdx.x;
   const int img = (int)(slot / p.spi), local = (int)(slot - (int64_t)img * p.spi);
@@ -377,8 +466,9 @@ __global__ void __launch_bounds__(256) je_len_kernel(je_params p, const int16_t*
     const je_pos pos = slot_pos(p, local);
     const int16_t* ic = coefs + (int64_t)img * p.spi * 64;
     const int t = pos.c ? 1 : 0;
-    walk_block(ic + (int64_t)local * 64, pred_dc(p, ic, local, pos), tables + 16 * t, tables + 32 + 256 * t,
-               [&](uint32_t, int len) { bits += len; });
+    const uint32_t* tab = tables + (int64_t)img * table_stride;
+    walk_block(ic + (int64_t)local * 64, pred_dc(p, ic, local, pos),
+               [&](int ac, int symbol, uint32_t, int size) { bits += (tab[table_word(t, ac, symbol)] >> 16) + size; });
   }
   lens[slot] = bits;
   uint32_t tot;
@@ -430,7 +520,7 @@ struct je_writer {
 };
 
 __global__ void __launch_bounds__(256) je_emit_kernel(je_params p, const int16_t* __restrict__ coefs,
-                                                      const uint32_t* __restrict__ tables,
+                                                      const uint32_t* __restrict__ tables, int table_stride,
                                                       const uint32_t* __restrict__ lens,
                                                       const uint64_t* __restrict__ chunk_off,
                                                       const uint64_t* __restrict__ word0, uint32_t* __restrict__ words) {
@@ -450,9 +540,40 @@ __global__ void __launch_bounds__(256) je_emit_kernel(je_params p, const int16_t
   const je_pos pos = slot_pos(p, local);
   const int16_t* ic = coefs + (int64_t)img * p.spi * 64;
   const int t = pos.c ? 1 : 0;
-  walk_block(ic + (int64_t)local * 64, pred_dc(p, ic, local, pos), tables + 16 * t, tables + 32 + 256 * t,
-             [&](uint32_t code, int l) { wr.put(code, l); });
+  const uint32_t* tab = tables + (int64_t)img * table_stride;
+  walk_block(ic + (int64_t)local * 64, pred_dc(p, ic, local, pos), [&](int ac, int symbol, uint32_t value, int size) {
+    const uint32_t e = tab[table_word(t, ac, symbol)];
+    wr.put(((e & 0xFFFF) << size) | value, (int)(e >> 16) + size);
+  });
   wr.finish();
+}
+
+// ---- ES: symbol statistics (optimize) ---------------------------------------------------------------------------
+// One thread per slot, E2's geometry: an image owns whole 256-slot chunks, so a workgroup counts for ONE image.  It
+// counts into its own histogram in LDS (LDS atomics) and then adds the bins it touched to the image's histogram
+// (hist: [n][JE_TABLE_WORDS], zeroed before the launch, laid out like a table set).  Integer sums: the result does not
+// depend on the order of arrival.
+__global__ void __launch_bounds__(256) je_stat_kernel(je_params p, const int16_t* __restrict__ coefs,
+                                                      uint32_t* __restrict__ hist) {
+  __shared__ uint32_t h[JE_TABLE_WORDS];
+  for (int k = threadIdx.x; k < JE_TABLE_WORDS; k += 256) h[k] = 0;
+  __syncthreads();
+  const int64_t slot = (int64_t)blockIdx.x * JE_SLOTS + threadIdx.x;
+  const int img = (int)(slot / p.spi), local = (int)(slot - (int64_t)img * p.spi);
+  if (img < p.n && local < p.nblocks) {
+    const je_pos pos = slot_pos(p, local);
+    const int16_t* ic = coefs + (int64_t)img * p.spi * 64;
+    const int t = pos.c ? 1 : 0;
+    walk_block(ic + (int64_t)local * 64, pred_dc(p, ic, local, pos),
+               [&](int ac, int symbol, uint32_t, int) { atomicAdd(&h[table_word(t, ac, symbol)], 1u); });
+  }
+  __syncthreads();
+  const int wimg = (int)((int64_t)blockIdx.x * JE_SLOTS / p.spi);   // the workgroup's image (p.spi is a multiple of 256)
+  if (wimg >= p.n) return;
+  for (int k = threadIdx.x; k < JE_TABLE_WORDS; k += 256) {
+    const uint32_t v = h[k];
+    if (v) atomicAdd(hist + (int64_t)wimg * JE_TABLE_WORDS + k, v);
+  }
 }
 
 // ---- E4 ---------------------------------------------------------------------------------------------------------
@@ -517,13 +638,17 @@ __global__ void __launch_bounds__(256) je_pack_kernel(const uint32_t* __restrict
                                                       const uint64_t* __restrict__ ff_off,
                                                       const uint64_t* __restrict__ ff_tot,
                                                       const uint64_t* __restrict__ file_off,
-                                                      const uint8_t* __restrict__ header, int header_len,
+                                                      const uint8_t* __restrict__ headers,
+                                                      const uint2* __restrict__ header_tab,
                                                       uint8_t* __restrict__ out) {
   __shared__ uint32_t lds[4];
   const int64_t chunk = blockIdx.x;
   const int img = find_image(seg, n, chunk);
   const int64_t rel = chunk - seg[img];
   const int64_t at = rel * JE_FF_CHUNK + threadIdx.x * 16;
+  const uint2 hd = header_tab[img];                            // the image's header: byte offset in `headers`, length
+  const uint8_t* header = headers + hd.x;
+  const int header_len = (int)hd.y;
   uint8_t b[16];
   const int real = load16(words + word0[img], bits, img, at, b);
   uint32_t cnt = 0;
@@ -563,8 +688,23 @@ extern "C" int ta_jpeg_encode_header(int h, int w, int quality, int subsampling,
   return TA_OK;
 }
 
-extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, const uint8_t** out,
-                              size_t* sizes) {
+extern "C" int ta_jpeg_optimal_table(const int64_t* freq, uint8_t* bits, uint8_t* vals, int* nvals) {
+  if (!freq || !bits || !vals || !nvals) return TA_E_INVALID;
+  bool any = false;
+  for (int i = 0; i < 256; ++i) {
+    if (freq[i] < 0 || freq[i] >= JE_MAX_COUNT) return TA_E_INVALID;
+    any |= freq[i] != 0;
+  }
+  je_huff t;
+  if (!any || !optimal_table(freq, &t)) return TA_E_INVALID;
+  memcpy(bits, t.bits, 17);
+  memcpy(vals, t.vals, (size_t)t.nvals);
+  *nvals = t.nvals;
+  return TA_OK;
+}
+
+static int jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, bool optimize,
+                       const uint8_t** out, size_t* sizes) {
   if (!ctx) return TA_E_INVALID;
   ta_enter(ctx);
   if (!frames || !out || !sizes) return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: bad arguments");
@@ -593,22 +733,33 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   }
   const int64_t nblocks = (int64_t)p.mcus_x * p.mcus_y * p.bpm;
   if (nblocks > (1ll << 30)) return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: image too large");
+  if (optimize && nblocks * 64 >= JE_MAX_COUNT)
+    return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: %lld blocks an image are too many for optimize (symbol counts must "
+                   "stay below 10^9)", (long long)nblocks);
   p.nblocks = (int)nblocks;
   p.spi = (int)align_up(nblocks, JE_SLOTS);
   const int64_t slots = (int64_t)n * p.spi, chunks = slots / JE_SLOTS;
   const std::vector<uint8_t> header = make_header(h, w, quality, subsampling);
   const int header_len = (int)header.size();
 
-  // phase 1 staging: [quant 2x64 u16][dc codes 2x16 u32, ac codes 2x256 u32][header][block segments n+1 i64]
-  const int64_t off_tables = 256, off_header = off_tables + (32 + 512) * 4;
-  const int64_t off_seg = align_up(off_header + header_len, 256);
+  // phase 1 staging: [quant 2x64 u16][dc codes 2x16 u32, ac codes 2x256 u32][header][header table n x (offset, length)
+  // u32][block segments n+1 i64]
+  const int64_t off_tables = 256, off_header = off_tables + JE_TABLE_WORDS * 4;
+  const int64_t off_htab = align_up(off_header + header_len, 8);
+  const int64_t off_seg = align_up(off_htab + (int64_t)n * 8, 256);
   const int64_t staged = align_up(off_seg + (int64_t)(n + 1) * 8, 256);
   // pinned after the staging: image bit totals, then phase 2 [word0 n][ff segments n+1], ff totals, file offsets
   const int64_t pin_bits = staged, pin_w0 = pin_bits + align_up(8 * n, 256);
   const int64_t pin_ffseg = pin_w0 + align_up(8 * n, 256), pin_fftot = pin_ffseg + align_up(8 * (n + 1), 256);
   const int64_t pin_foff = pin_fftot + align_up(8 * n, 256), pin_end = pin_foff + align_up(8 * n, 256);
+  // optimize: the histograms come here; the per-image [code words][headers][header table] go back in one copy
+  const int64_t set_bytes = (int64_t)JE_TABLE_WORDS * 4;
+  const int64_t pin_hist = pin_end, pin_otab = pin_hist + align_up(n * set_bytes, 256);
+  const int64_t pin_ohdr = pin_otab + align_up(n * set_bytes, 256);
+  const int64_t pin_ohtab = pin_ohdr + (int64_t)n * JE_HEADER_STRIDE;
+  const int64_t pin_all = optimize ? pin_ohtab + align_up(8 * n, 256) : pin_end;
   void* pin = nullptr;
-  TA_TRY(ta_pinned(ctx, (size_t)pin_end, &pin));
+  TA_TRY(ta_pinned(ctx, (size_t)pin_all, &pin));
   uint8_t* host = (uint8_t*)pin;
   quant_table(quality, 0, (uint16_t*)host);
   quant_table(quality, 1, (uint16_t*)host + 64);
@@ -618,6 +769,11 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   huff_codes(kAcLumaBits, kAcLumaVals, tab + 32, 256);
   huff_codes(kAcChromaBits, kAcChromaVals, tab + 32 + 256, 256);
   memcpy(host + off_header, header.data(), header.size());
+  uint32_t* htab = (uint32_t*)(host + off_htab);               // every image: the one shared header
+  for (int i = 0; i < n; ++i) {
+    htab[2 * i] = 0;
+    htab[2 * i + 1] = (uint32_t)header_len;
+  }
   int64_t* seg = (int64_t*)(host + off_seg);
   for (int i = 0; i <= n; ++i) seg[i] = (int64_t)i * (p.spi / JE_SLOTS);
 
@@ -625,18 +781,26 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   const int64_t d_coef = staged, d_lens = d_coef + slots * 128, d_ctot = align_up(d_lens + slots * 4, 256);
   const int64_t d_coff = align_up(d_ctot + chunks * 4, 256), d_bits = align_up(d_coff + chunks * 8, 256);
   const int64_t d_p2 = d_bits + align_up(8 * n, 256);   // phase 2 copies of pin_w0 .. pin_end
-  const int64_t d_end = d_p2 + (pin_end - pin_w0);
+  const int64_t d_hist = d_p2 + (pin_end - pin_w0);     // optimize: histograms, then the copies of pin_otab .. pin_all
+  const int64_t d_opt = d_hist + (pin_otab - pin_hist);
+  const int64_t d_end = optimize ? d_opt + (pin_all - pin_otab) : d_hist;
   void* scr = nullptr;
   TA_TRY(ta_scratch(ctx, (size_t)d_end, &scr));
   uint8_t* dev = (uint8_t*)scr;
   const uint16_t* d_quant = (const uint16_t*)dev;
-  const uint32_t* d_tables = (const uint32_t*)(dev + off_tables);
+  const uint32_t* d_tables = (const uint32_t*)(optimize ? dev + d_opt : dev + off_tables);
+  const int table_stride = optimize ? JE_TABLE_WORDS : 0;
+  const uint8_t* d_headers = optimize ? dev + d_opt + (pin_ohdr - pin_otab) : dev + off_header;
+  const uint2* d_htab = (const uint2*)(optimize ? dev + d_opt + (pin_ohtab - pin_otab) : dev + off_htab);
+  if (optimize) htab = (uint32_t*)(host + pin_ohtab);
+  const int header_cap = optimize ? JE_HEADER_STRIDE : header_len;
   uint64_t* d_bits_p = (uint64_t*)(dev + d_bits);
   auto p2 = [&](int64_t pin_off) { return dev + d_p2 + (pin_off - pin_w0); };
 
   // HIP events around each pass while profiling: [0] H2D staging, [1] E1, [2] E2 + scan, [3] E3, [4] E4a + scan,
-  // [5] E4b, [6] D2H of the files
-  hipEvent_t ev[14] = {};
+  // [5] E4b, [6] D2H of the files; [7] the statistics pass (optimize)
+  hipEvent_t ev[16] = {};
+  double opt_ms[2] = {0, 0};
   const bool timed = ctx->profiling;
   if (timed)
     for (auto& e : ev)
@@ -647,16 +811,17 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   auto done = [&](hipError_t e) {
     double ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (timed) {
-      for (int k = 0; k < 7; ++k) {
+      for (int k = 0; k < (optimize ? 8 : 7); ++k) {
         float f = 0;
         if (e == hipSuccess && ev[2 * k] && ev[2 * k + 1] && hipEventElapsedTime(&f, ev[2 * k], ev[2 * k + 1]) == hipSuccess)
-          ms[k] = f;
+          (k < 7 ? ms[k] : opt_ms[0]) = f;
       }
       for (auto& x : ev)
         if (x) (void)hipEventDestroy(x);
     }
     ms[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
     memcpy(ctx->jpeg_enc_ms, ms, sizeof(ms));
+    memcpy(ctx->jpeg_enc_opt_ms, opt_ms, sizeof(opt_ms));
     return e;
   };
 
@@ -671,10 +836,53 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
     e = hipGetLastError();
   }
   mark(3);
+  if (optimize) {
+    // ES: the histograms to the host, which builds every image's tables and header and sends them back
+    uint32_t* d_hist_p = (uint32_t*)(dev + d_hist);
+    mark(14);
+    if (e == hipSuccess) e = hipMemsetAsync(d_hist_p, 0, (size_t)(n * set_bytes), ctx->stream);
+    if (e == hipSuccess) {
+      hipLaunchKernelGGL(je_stat_kernel, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, p,
+                         (const int16_t*)(dev + d_coef), d_hist_p);
+      e = hipGetLastError();
+    }
+    mark(15);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(host + pin_hist, d_hist_p, (size_t)(n * set_bytes), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return ta_fail(ctx, TA_E_DEVICE, "jpeg_encode: %s", hipGetErrorString(done(e)));
+    const auto t_tab = std::chrono::steady_clock::now();
+    for (int i = 0; i < n; ++i) {
+      const uint32_t* hist = (const uint32_t*)(host + pin_hist) + (int64_t)i * JE_TABLE_WORDS;
+      uint32_t* codes = (uint32_t*)(host + pin_otab) + (int64_t)i * JE_TABLE_WORDS;
+      je_huff huff[4];                                         // DC 0, AC 0, DC 1, AC 1: the order of the DHT segments
+      for (int k = 0; k < 4; ++k) {
+        const int t = k >> 1, ac = k & 1, nsym = ac ? 256 : 16, at = ac ? 32 + 256 * t : 16 * t;
+        int64_t freq[257] = {};
+        for (int s = 0; s < nsym; ++s) freq[s] = hist[at + s];
+        if (!optimal_table(freq, &huff[k])) {
+          (void)done(hipSuccess);
+          return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: image %d needs a Huffman code longer than 32 bits", i);
+        }
+        huff_codes(huff[k].bits + 1, huff[k].vals, codes + at, nsym);
+      }
+      const std::vector<uint8_t> hd = make_header(h, w, quality, subsampling, huff);
+      if (hd.size() > JE_HEADER_STRIDE) {
+        (void)done(hipSuccess);
+        return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: header of %zu bytes", hd.size());
+      }
+      memcpy(host + pin_ohdr + (int64_t)i * JE_HEADER_STRIDE, hd.data(), hd.size());
+      htab[2 * i] = (uint32_t)(i * JE_HEADER_STRIDE);
+      htab[2 * i + 1] = (uint32_t)hd.size();
+    }
+    opt_ms[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tab).count();
+    e = hipMemcpyAsync(dev + d_opt, host + pin_otab, (size_t)(pin_all - pin_otab), hipMemcpyHostToDevice, ctx->stream);
+  }
   mark(4);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(je_len_kernel, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, p,
-                       (const int16_t*)(dev + d_coef), d_tables, (uint32_t*)(dev + d_lens), (uint32_t*)(dev + d_ctot));
+                       (const int16_t*)(dev + d_coef), d_tables, table_stride, (uint32_t*)(dev + d_lens),
+                       (uint32_t*)(dev + d_ctot));
     e = hipGetLastError();
   }
   if (e == hipSuccess) {
@@ -704,7 +912,7 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   // second device block: [words][ff counts][ff offsets][ff totals][packed files, worst case: every byte stuffed]
   const int64_t e_ffc = words * 4, e_ffo = align_up(e_ffc + ffchunks * 4, 256);
   const int64_t e_fft = align_up(e_ffo + ffchunks * 8, 256), e_out = e_fft + align_up(8 * n, 256);
-  const int64_t e_end = e_out + 2 * entropy_bytes + (int64_t)n * (header_len + 2);
+  const int64_t e_end = e_out + 2 * entropy_bytes + (int64_t)n * (header_cap + 2);
   if ((size_t)e_end > ctx->jpeg_enc_dev_bytes) {
     if (ctx->jpeg_enc_dev) (void)hipFree(ctx->jpeg_enc_dev);  // the stream is idle: synchronised above
     ctx->jpeg_enc_dev = nullptr;
@@ -725,7 +933,7 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   mark(6);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(je_emit_kernel, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, p,
-                       (const int16_t*)(dev + d_coef), d_tables, (const uint32_t*)(dev + d_lens),
+                       (const int16_t*)(dev + d_coef), d_tables, table_stride, (const uint32_t*)(dev + d_lens),
                        (const uint64_t*)(dev + d_coff), d_w0, d_words);
     e = hipGetLastError();
   }
@@ -751,7 +959,7 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   uint64_t* foff = (uint64_t*)(host + pin_foff);
   int64_t total = 0;
   for (int i = 0; i < n; ++i) {
-    sizes[i] = (size_t)(header_len + (int64_t)((bits[i] + 7) >> 3) + (int64_t)fftot[i] + 2);
+    sizes[i] = (size_t)((int64_t)htab[2 * i + 1] + (int64_t)((bits[i] + 7) >> 3) + (int64_t)fftot[i] + 2);
     foff[i] = (uint64_t)total;
     total += (int64_t)sizes[i];
   }
@@ -769,7 +977,7 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   if (e == hipSuccess) {
     hipLaunchKernelGGL(je_pack_kernel, dim3((unsigned)ffchunks), dim3(256), 0, ctx->stream, d_words, d_w0, d_bits_p,
                        d_ffseg, n, (const uint64_t*)(eb + e_ffo), (const uint64_t*)(eb + e_fft),
-                       (const uint64_t*)p2(pin_foff), (const uint8_t*)(dev + off_header), header_len, eb + e_out);
+                       (const uint64_t*)p2(pin_foff), d_headers, d_htab, eb + e_out);
     e = hipGetLastError();
   }
   mark(11);
@@ -785,6 +993,26 @@ extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality,
   ctx->jpeg_enc_counts[2] = total;
   ctx->jpeg_enc_counts[3] = entropy_bytes;
   *out = ctx->jpeg_enc_out;
+  return TA_OK;
+}
+
+extern "C" int ta_jpeg_encode(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, const uint8_t** out,
+                              size_t* sizes) {
+  return jpeg_encode(ctx, frames, quality, subsampling, false, out, sizes);
+}
+
+extern "C" int ta_jpeg_encode_opt(ta_ctx* ctx, const ta_frames* frames, int quality, int subsampling, int optimize,
+                                  const uint8_t** out, size_t* sizes) {
+  if (ctx && optimize != 0 && optimize != 1) {
+    ta_enter(ctx);
+    return ta_fail(ctx, TA_E_INVALID, "jpeg_encode: optimize %d not 0 or 1", optimize);
+  }
+  return jpeg_encode(ctx, frames, quality, subsampling, optimize == 1, out, sizes);
+}
+
+extern "C" int ta_jpeg_encode_last_opt_stats(const ta_ctx* ctx, double* ms) {
+  if (!ctx || !ms) return TA_E_INVALID;
+  memcpy(ms, ctx->jpeg_enc_opt_ms, sizeof(ctx->jpeg_enc_opt_ms));
   return TA_OK;
 }
 

@@ -125,6 +125,7 @@ struct ta_ctx {
   int64_t jpeg_counts[4] = {0, 0, 0, 0};
   double jpeg_enc_ms[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // figures of the last ta_jpeg_encode (ta_jpeg_encode_last_stats)
   int64_t jpeg_enc_counts[4] = {0, 0, 0, 0};
+  double jpeg_enc_opt_ms[2] = {0, 0};              // optimize=1 only: statistics pass, host table + header build
   void* jpeg_enc_dev = nullptr;                    // ta_jpeg_encode's second device block (bit words + packed files), grow-only
   size_t jpeg_enc_dev_bytes = 0;
   uint8_t* jpeg_enc_out = nullptr;                 // pinned: the files of the last ta_jpeg_encode, grow-only

@@ -18,7 +18,9 @@ Out: `encode_jpeg(images, quality, subsampling)` encodes resident batches (or ho
 (`ta_jpeg_encode`) into JPEG files that are byte for byte what Pillow's `Image.fromarray(frame).save(f, 'JPEG',
 quality=quality, subsampling=subsampling)` writes; only the compressed bytes leave the device.  `save_images` writes
 them to files.  Pillow's argument semantics: quality 1..100 (default 75), subsampling -1 (default: 4:2:0), 0 / '4:4:4',
-1 / '4:2:2', 2 / '4:2:0'.  Other options (progressive, optimize, qtables, dpi, exif, ...) are not offered.
+1 / '4:2:2', 2 / '4:2:0'; optimize=True codes every image with Huffman tables built from its own statistics
+(`ta_jpeg_encode_opt`: smaller files, the same pixels), again Pillow's bytes.  Other options (progressive, qtables, dpi,
+exif, ...) are not offered.
 """
 import os
 from pathlib import Path
@@ -179,8 +181,10 @@ def _tag(frames, paths):
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}
 
 
-def jpeg_options(quality=75, subsampling=-1):
-    """Pillow's save() arguments -> (quality, subsampling code for ta_jpeg_encode); ValueError for anything else."""
+def jpeg_options(quality=75, subsampling=-1, optimize=False):
+    """Pillow's save() arguments -> (quality, subsampling code for ta_jpeg_encode); ValueError for anything else
+    (`optimize` must be True or False)."""
+    lib.check_jpeg_optimize(optimize)
     key = subsampling if isinstance(subsampling, str) else (
         int(subsampling) if isinstance(subsampling, (int, np.integer)) and not isinstance(subsampling, bool) else None)
     if key not in _SUBSAMPLING:
@@ -188,11 +192,11 @@ def jpeg_options(quality=75, subsampling=-1):
     return lib.check_jpeg_options(quality, _SUBSAMPLING[key])
 
 
-def encode_jpeg(images, quality=75, subsampling=-1, ctx=None, device=None):
+def encode_jpeg(images, quality=75, subsampling=-1, ctx=None, device=None, optimize=False):
     """Resident frames -> JPEG files (list of bytes, one per frame, in order).  `images`: a `lib.Frames` batch, a list of
     them (as `open_images` returns for mixed sizes), or a host uint8 (H, W, 3) / (N, H, W, 3) array (uploaded first).
-    Every option is checked before anything is launched."""
-    quality, code = jpeg_options(quality, subsampling)
+    `optimize`: Pillow's optimize=True.  Every option is checked before anything is launched."""
+    quality, code = jpeg_options(quality, subsampling, optimize)
     if isinstance(images, lib.Frames):
         batches = [images]
     elif isinstance(images, (list, tuple)):
@@ -209,7 +213,7 @@ def encode_jpeg(images, quality=75, subsampling=-1, ctx=None, device=None):
         ctx = ctx if ctx is not None else runtime.get_context(device)
         up = ctx.upload(arr[None] if arr.ndim == 3 else arr)
         try:
-            return ctx.jpeg_encode(up, quality, code)
+            return ctx.jpeg_encode(up, quality, code, optimize)
         finally:
             up.free()
     for b in batches:
@@ -217,14 +221,14 @@ def encode_jpeg(images, quality=75, subsampling=-1, ctx=None, device=None):
             raise ValueError('encode_jpeg: JPEG sides are at most 65535 pixels')
     files = []
     for b in batches:
-        files.extend(b.encode_jpeg(quality, code, ctx=ctx))
+        files.extend(b.encode_jpeg(quality, code, ctx=ctx, optimize=optimize))
     return files
 
 
-def save_images(images, paths, quality=75, subsampling=-1, ctx=None, device=None):
+def save_images(images, paths, quality=75, subsampling=-1, ctx=None, device=None, optimize=False):
     """encode_jpeg(images, ...) written to `paths` (one per frame, in order)."""
     paths = list(paths)
-    jpeg_options(quality, subsampling)
+    jpeg_options(quality, subsampling, optimize)
     if isinstance(images, lib.Frames):
         n = images.shape[0]
     elif isinstance(images, (list, tuple)):
@@ -234,7 +238,7 @@ def save_images(images, paths, quality=75, subsampling=-1, ctx=None, device=None
         n = 1 if len(shape) == 3 else (shape[0] if shape else 0)
     if n != len(paths):
         raise ValueError('save_images: %d frames, %d paths' % (n, len(paths)))
-    files = encode_jpeg(images, quality, subsampling, ctx=ctx, device=device)
+    files = encode_jpeg(images, quality, subsampling, ctx=ctx, device=device, optimize=optimize)
     for data, path in zip(files, paths):
         with open(_path(path), 'wb') as fh:
             fh.write(data)

@@ -59,6 +59,9 @@ SIGNATURES = {
     'ta_jpeg_encode_header': (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_size_t, P(c_size_t)]),
     'ta_jpeg_encode': (c_int, [c_void_p, c_void_p, c_int, c_int, P(c_void_p), P(c_size_t)]),
     'ta_jpeg_encode_last_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'ta_jpeg_encode_opt': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_void_p), P(c_size_t)]),
+    'ta_jpeg_optimal_table': (c_int, [c_void_p, c_void_p, c_void_p, P(c_int)]),
+    'ta_jpeg_encode_last_opt_stats': (c_int, [c_void_p, c_void_p]),
     'ta_model_load': (c_int, [c_void_p, c_int, c_void_p, c_size_t, P(c_void_p)]),
     'ta_model_free': (None, [c_void_p]),
     'ta_model_kind': (c_int, [c_void_p]),
@@ -142,6 +145,20 @@ def jpeg_encode_header(h, w, quality=75, subsampling=2):
     return buf[:size.value].tobytes()
 
 
+def jpeg_optimal_table(freq):
+    """Host only (no context, no device): ta_jpeg_optimal_table -> (counts of codes of length 1..16, symbols in code
+    order) of libjpeg's optimal Huffman table for the symbol frequencies freq[0..255] (a 257th entry is ignored)."""
+    lib = load()
+    f = np.zeros(257, np.int64)
+    freq = np.asarray(freq, np.int64).reshape(-1)
+    f[:min(256, freq.size)] = freq[:256]
+    bits, vals, n = np.zeros(17, np.uint8), np.zeros(256, np.uint8), c_int()
+    rc = lib.ta_jpeg_optimal_table(ptr(f), ptr(bits), ptr(vals), C.byref(n))
+    if rc != OK:
+        raise TerranAmdError(rc, 'jpeg_optimal_table: frequencies must be 0 .. 10^9 - 1 and not all zero')
+    return bits[1:].tolist(), vals[:n.value].tolist()
+
+
 def check_jpeg_options(quality, subsampling):
     """The encoder's options as ints, or ValueError (before anything is launched): quality 1..100, subsampling 0 / 1 / 2."""
     if isinstance(quality, bool) or not isinstance(quality, (int, np.integer)) or not 1 <= quality <= 100:
@@ -149,6 +166,13 @@ def check_jpeg_options(quality, subsampling):
     if isinstance(subsampling, bool) or not isinstance(subsampling, (int, np.integer)) or subsampling not in (0, 1, 2):
         raise ValueError('JPEG subsampling must be 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0), got %r' % (subsampling,))
     return int(quality), int(subsampling)
+
+
+def check_jpeg_optimize(optimize):
+    """Pillow's `optimize` as a bool, or ValueError (before anything is launched)."""
+    if not isinstance(optimize, (bool, np.bool_)):
+        raise ValueError('JPEG optimize must be True or False, got %r' % (optimize,))
+    return bool(optimize)
 
 
 # conv kernel variants (include/terran_amd.h TA_CONV_*)
@@ -314,14 +338,19 @@ class Context:
         return (dict(zip(('host', 'h2d', 'idct', 'color'), ms.tolist())),
                 dict(zip(('images', 'blocks', 'bytes', 'fallbacks'), cnt.tolist())))
 
-    def jpeg_encode(self, frames, quality=75, subsampling=2):
+    def jpeg_encode(self, frames, quality=75, subsampling=2, optimize=False):
         """ta_jpeg_encode: a resident Frames batch -> list of JPEG files (bytes), Pillow's for the same options; runs on
-        this context's stream (ordered after a draw on it)."""
+        this context's stream (ordered after a draw on it).  `optimize`: Pillow's optimize=True, every image coded with
+        its own Huffman tables (ta_jpeg_encode_opt)."""
         quality, subsampling = check_jpeg_options(quality, subsampling)
+        optimize = check_jpeg_optimize(optimize)
         n = frames.shape[0]
         out = c_void_p()
         sizes = (c_size_t * n)()
-        self.check(self.lib.ta_jpeg_encode(self.h, frames.h, quality, subsampling, C.byref(out), sizes))
+        if optimize:
+            self.check(self.lib.ta_jpeg_encode_opt(self.h, frames.h, quality, subsampling, 1, C.byref(out), sizes))
+        else:
+            self.check(self.lib.ta_jpeg_encode(self.h, frames.h, quality, subsampling, C.byref(out), sizes))
         files, at = [], out.value
         for k in range(n):
             files.append(C.string_at(at, sizes[k]))
@@ -329,11 +358,14 @@ class Context:
         return files
 
     def jpeg_encode_stats(self):
-        """Figures of the last jpeg_encode: ({h2d, coef, length, emit, ffcount, pack, d2h, host}: ms),
-        {images, blocks, bytes, entropy_bytes}."""
-        ms, cnt = np.zeros(8, np.float64), np.zeros(4, np.int64)
+        """Figures of the last jpeg_encode: ({h2d, coef, length, emit, ffcount, pack, d2h, host; statistics, tables}:
+        ms), {images, blocks, bytes, entropy_bytes}.  `statistics` (the symbol-count pass, HIP events) and `tables` (the
+        host building tables and headers, wall time) are 0 unless the call had optimize=True."""
+        ms, cnt, opt = np.zeros(8, np.float64), np.zeros(4, np.int64), np.zeros(2, np.float64)
         self.check(self.lib.ta_jpeg_encode_last_stats(self.h, ptr(ms), ptr(cnt)))
-        return (dict(zip(('h2d', 'coef', 'length', 'emit', 'ffcount', 'pack', 'd2h', 'host'), ms.tolist())),
+        self.check(self.lib.ta_jpeg_encode_last_opt_stats(self.h, ptr(opt)))
+        return (dict(zip(('h2d', 'coef', 'length', 'emit', 'ffcount', 'pack', 'd2h', 'host', 'statistics', 'tables'),
+                         ms.tolist() + opt.tolist())),
                 dict(zip(('images', 'blocks', 'bytes', 'entropy_bytes'), cnt.tolist())))
 
     def conv_variant(self, name):
@@ -448,10 +480,10 @@ class Frames:
         masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
         ctx.check(ctx.lib.ta_frames_draw_masks(ctx.h, self.h, pp, len(prims), ptr(masks) if len(masks) else None, len(masks)))
 
-    def encode_jpeg(self, quality=75, subsampling=2, ctx=None):
+    def encode_jpeg(self, quality=75, subsampling=2, ctx=None, optimize=False):
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs
         on -- the CALLER's, as in `draw`, so it is ordered after a draw on that context."""
-        return (ctx or self.ctx).jpeg_encode(self, quality, subsampling)
+        return (ctx or self.ctx).jpeg_encode(self, quality, subsampling, optimize)
 
     def download(self):
         out = np.empty(self.shape, np.uint8)

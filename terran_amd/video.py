@@ -158,14 +158,15 @@ class JpegVideoWriter:
 
     Encoding runs on the calling thread's context (ordered after a draw on it); a daemon thread writes the files to
     `stream` through a queue of at most `buffer_size` frames.  A write error is raised by the next call; writing after
-    `close()` raises VideoClosed.  `encoder(images, quality, subsampling) -> list of bytes` replaces the GPU encoder
-    (tests)."""
+    `close()` raises VideoClosed.  `optimize`: Pillow's optimize=True, per-frame Huffman tables (a smaller stream).
+    `encoder(images, quality, subsampling) -> list of bytes` replaces the GPU encoder (tests); with optimize=True it is
+    called as `encoder(images, quality, subsampling, optimize=True)`."""
 
     def __init__(self, stream, quality=75, subsampling=-1, buffer_size=DEFAULT_WRITER_BUFFER_SIZE, device=None,
-                 encoder=None):
+                 encoder=None, optimize=False):
         from . import image
-        image.jpeg_options(quality, subsampling)            # bad options fail here, before any frame
-        self.stream, self.quality, self.subsampling = stream, quality, subsampling
+        image.jpeg_options(quality, subsampling, optimize)  # bad options fail here, before any frame
+        self.stream, self.quality, self.subsampling, self.optimize = stream, quality, subsampling, bool(optimize)
         self.frames_written = 0
         self._device = device
         self._encoder = encoder
@@ -201,9 +202,11 @@ class JpegVideoWriter:
 
     def _encode(self, images):
         if self._encoder is not None:
+            if self.optimize:
+                return self._encoder(images, self.quality, self.subsampling, optimize=True)
             return self._encoder(images, self.quality, self.subsampling)
         from . import image
-        return image.encode_jpeg(images, self.quality, self.subsampling, device=self._device)
+        return image.encode_jpeg(images, self.quality, self.subsampling, device=self._device, optimize=self.optimize)
 
     def write_frames(self, batch):
         """Encode every frame of `batch` (a lib.Frames batch, a list of them, or host uint8 (N, H, W, 3)) and queue the

@@ -6,8 +6,11 @@ quarter of the size, bicubic-upscaled) and a uniform-noise batch; each at q75 an
 Reported per set, quality and leg: images/s (wall), host CPU-seconds per image (process CPU time over the timed loop,
 every thread) and bytes copied device to host; for the device path also the HIP-event time of each pass
 (ta_jpeg_encode_last_stats with profiling on).  The Pillow legs need Pillow (skipped, and said so, without it).
+--optimize adds, per set and quality, the same device leg with optimize=True (per-image Huffman tables): its images/s,
+host CPU, bytes to host, pass times (with `statistics`, the symbol-count pass, and `tables`, the host's table building)
+and the size of its files over the standard ones; --no-pillow leaves the Pillow legs out.
 
-    python tools/jpeg_encode_bench.py [--reps 5] [--json out.json]
+    python tools/jpeg_encode_bench.py [--reps 5] [--optimize] [--no-pillow] [--json out.json]
 """
 import argparse
 import io
@@ -70,9 +73,9 @@ def pillow_leg(frames, quality, threads, reps):
             pool.shutdown()
 
 
-def device_leg(ctx, frames, quality, reps):
+def device_leg(ctx, frames, quality, reps, optimize=False):
     def run():
-        return frames.encode_jpeg(quality, 2, ctx=ctx)
+        return frames.encode_jpeg(quality, 2, ctx=ctx, optimize=optimize)
     wall, cpu = timed(run, reps)
     ctx.profile(True)
     files = run()
@@ -85,6 +88,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--json', default=None)
+    ap.add_argument('--optimize', action='store_true', help='also measure optimize=True')
+    ap.add_argument('--no-pillow', action='store_true', help='skip the download + Pillow legs')
     a = ap.parse_args()
     ctx = runtime.get_context(0)
     try:
@@ -102,14 +107,22 @@ def main():
             wall, cpu, ms, counts, files = device_leg(ctx, frames, quality, a.reps)
             row['device'] = {'img_per_s': N / wall, 'cpu_ms_per_img': 1e3 * cpu / N, 'd2h_mb': counts['bytes'] / 1e6,
                              'pass_ms': {k: round(v, 4) for k, v in ms.items()}, 'blocks': counts['blocks']}
-            for threads in (1, 16):
+            if a.optimize:
+                standard_bytes = sum(len(f) for f in files)
+                wall, cpu, ms, counts, files = device_leg(ctx, frames, quality, a.reps, optimize=True)
+                row['device_optimize'] = {'img_per_s': N / wall, 'cpu_ms_per_img': 1e3 * cpu / N,
+                                          'd2h_mb': counts['bytes'] / 1e6,
+                                          'pass_ms': {k: round(v, 4) for k, v in ms.items()},
+                                          'size_ratio': sum(len(f) for f in files) / standard_bytes,
+                                          'speed_vs_standard': N / wall / row['device']['img_per_s']}
+            for threads in (() if a.no_pillow else (1, 16)):
                 if have_pil:
                     wall, cpu = pillow_leg(frames, quality, threads, max(1, a.reps // (2 if threads == 1 else 1)))
                     row['pillow_t%d' % threads] = {'img_per_s': N / wall, 'cpu_ms_per_img': 1e3 * cpu / N,
                                                    'd2h_mb': host.nbytes / 1e6}
                 else:
                     row['pillow_t%d' % threads] = 'not measured: Pillow absent'
-            if have_pil:
+            if have_pil and not a.no_pillow:
                 row['speedup_vs_pillow_t16'] = row['device']['img_per_s'] / row['pillow_t16']['img_per_s']
             name = '%s_q%d' % (kind, quality)
             report[name] = row
