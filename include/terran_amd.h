@@ -135,6 +135,37 @@ int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, in
 int ta_frames_draw_masks(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, const uint8_t* masks,
                          size_t mask_bytes);
 
+/* ---- blurring regions (anonymising faces) ---------------------------------------------- */
+/* Blurs rectangles of `frames` in place, Pillow's
+ *     region = im.crop(box).filter(ImageFilter.GaussianBlur(radius)); im.paste(region, box)
+ * bit for bit: three box-blur passes along the rows, then three along the columns, each rounded to uint8, the weights
+ * derived from `radius` in float32 as libImaging does.  The blur sees only the region's own pixels (edges are extended at
+ * the region's border, not the frame's).  The box [x0, x1) x [y0, y1) is half-open and must lie inside the frame.
+ *   TA_BLUR_BOX      every pixel of the box takes its blurred value.
+ *   TA_BLUR_ELLIPSE  only the pixels of ImageDraw.ellipse([0, 0, w - 1, h - 1], fill=) in the box do (TA_DRAW_DISC's
+ *                    coverage; a 1 x 1 box has none); the blur itself is still computed over the whole box.
+ * radius = 0 leaves the region as it is.  Regions of one frame are applied in list order: a later one blurs what an
+ * earlier one it overlaps left; regions of different frames may be interleaved.  The library sorts the regions into rounds
+ * of pairwise disjoint ones (the usual case: one round) and runs two kernels per round.  The call runs on `ctx`'s stream
+ * (a batch of another context on the same device may be blurred) and returns when it is done.  n = 0: TA_OK.
+ * TA_E_INVALID, before any pixel changes: frame index out of range; a box that is empty, inverted or not inside the
+ * frame, or has a side longer than 16384; unknown shape; a radius that is negative, NaN, infinite or above 1024. */
+#define TA_BLUR_BOX 0
+#define TA_BLUR_ELLIPSE 1
+typedef struct ta_blur_region {
+  int32_t frame;       /* image index in the batch                  */
+  int32_t x0, y0, x1, y1;
+  int32_t shape;       /* TA_BLUR_*                                 */
+  float radius;        /* GaussianBlur's radius (a standard deviation, in pixels) */
+} ta_blur_region;
+int ta_frames_blur(ta_ctx* ctx, ta_frames* frames, const ta_blur_region* regions, int n);
+/* HOST ONLY, no context: what ta_frames_blur derives from the regions before it launches anything.  rounds[i]: the round
+ * region i runs in (one more than the latest round of an earlier region of its frame that it intersects).
+ * box_radius[i]: the fractional radius of the box passes; weights[2 i], weights[2 i + 1]: the 2^-24 fixed-point weights
+ * of a window pixel and of the two pixels beside the window.  Any output may be NULL.  Frame indices only group the
+ * regions here.  TA_E_INVALID: an empty or inverted box, an unknown shape, a bad radius. */
+int ta_blur_plan(const ta_blur_region* regions, int n, int32_t* rounds, float* box_radius, uint32_t* weights);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

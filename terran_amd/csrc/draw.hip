@@ -471,6 +471,8 @@ int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool 
 
 }  // namespace
 
+void ta_disc_rows(int a, int b, std::vector<int2>& tab) { disc_rows(a, b, tab); }   // ta_frames_blur's ellipse shape
+
 extern "C" int ta_frames_draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n) {
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;

@@ -254,6 +254,9 @@ struct ta_frames {
   size_t cap = 0;          // bytes allocated
 };
 int ta_frames_alloc_uninit(ta_ctx* ctx, int n, int h, int w, ta_frames** out);   // ta_frames_alloc without the zero fill
+// draw.hip: Pillow's filled ellipse in the box [0, a] x [0, b] (ImageDraw.ellipse(fill=)), appended to `tab` as one pixel span
+// [lo, hi] per row 0..b (lo > hi: nothing in that row).  Host code; a and b at most 32768.
+void ta_disc_rows(int a, int b, std::vector<int2>& tab);
 
 // ---------------------------------------------------------------------------------------------
 // Planned tensors / kernels

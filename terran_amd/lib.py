@@ -52,6 +52,8 @@ SIGNATURES = {
     'ta_frames_paste': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int]),
     'ta_frames_draw': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_frames_draw_masks': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    'ta_frames_blur': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'ta_blur_plan': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -99,6 +101,26 @@ DRAW_BAR, DRAW_LINE, DRAW_DISC, DRAW_MASK = 0, 1, 2, 3
 PRIM_DT = np.dtype([('frame', '<i4'), ('kind', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'),
                     ('width', '<i4'), ('rgba', 'u1', (4,))])
 assert PRIM_DT.itemsize == 32
+
+# ta_blur_region (include/terran_amd.h) and its shapes TA_BLUR_*; the box is half-open
+BLUR_BOX, BLUR_ELLIPSE = 0, 1
+BLUR_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                    ('radius', '<f4')])
+assert BLUR_DT.itemsize == 28
+
+
+def blur_plan(regions):
+    """Host only (no context, no device): ta_blur_plan -> (round of every region, float32 box radius, uint32 (n, 2)
+    weights ww, fw): what ta_frames_blur derives from a BLUR_DT array before it launches anything."""
+    lib = load()
+    regions = np.ascontiguousarray(regions, dtype=BLUR_DT)
+    n = len(regions)
+    rounds, fr, w = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 2), np.uint32)
+    rc = lib.ta_blur_plan(ptr(regions) if n else None, n, ptr(rounds), ptr(fr), ptr(w))
+    if rc != OK:
+        raise TerranAmdError(rc, 'blur_plan: an empty or inverted box, an unknown shape or a bad radius')
+    return rounds, fr, w
+
 
 # ta_jpeg_header and the decode paths TA_JPEG_* (include/terran_amd.h)
 JPEG_DEVICE = 0
@@ -479,6 +501,13 @@ class Frames:
             return
         masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
         ctx.check(ctx.lib.ta_frames_draw_masks(ctx.h, self.h, pp, len(prims), ptr(masks) if len(masks) else None, len(masks)))
+
+    def blur(self, regions, ctx=None):
+        """Blur `regions` (a BLUR_DT array, in order) of this batch in place (ta_frames_blur): Pillow's GaussianBlur of each
+        half-open box, pasted back under its shape.  `ctx`: the context the blur runs on -- the CALLER's, as in `draw`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=BLUR_DT)
+        ctx.check(ctx.lib.ta_frames_blur(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
 
     def encode_jpeg(self, quality=75, subsampling=2, ctx=None, optimize=False):
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs

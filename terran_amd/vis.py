@@ -17,8 +17,13 @@ reference still calls, read as `getbbox(t)[2:4]` (what it returned).  The glyphs
 font (FreeType), once per distinct (font, size, text, fractional start): an LRU keeps the coverage bitmaps, and a call
 uploads each distinct one once, however many frames show it.  The tab is a bar, the text a DRAW_MASK primitive.
 
-Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch.
-Importing this module needs no GPU and no Pillow.
+Blurring (`blur_faces` in place on a resident batch, `anonymize_faces` on a host image; not in the reference): every
+face's box, int()-truncated and clipped to the frame, is replaced by Pillow's
+`im.crop(box).filter(ImageFilter.GaussianBlur(radius))` bit for bit (csrc/blur.hip), optionally only under the ellipse
+`ImageDraw.ellipse` draws into that box, so a video job makes its faces unrecognisable without downloading a frame.
+
+Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch, the
+blurring one ta_frames_blur call.  Importing this module needs no GPU and no Pillow.
 """
 import collections
 import math
@@ -336,7 +341,75 @@ def draw_poses(frames, poses_per_frame, scale=1.0, ctx=None):
     return frames
 
 
-def _on_host_image(image, prims, masks=None, device=None):
+# ---- blurring faces ----------------------------------------------------------------------------------------------------
+BLUR_SHAPES = {'box': lib.BLUR_BOX, 'ellipse': lib.BLUR_ELLIPSE}
+BLUR_RADIUS_LIMIT = 1024.0                              # what ta_frames_blur accepts
+
+
+def _frame_sizes(shapes, n):
+    """`shapes` of pack_blur -> (n, 2) int array of (H, W)."""
+    s = np.asarray(shapes, np.int64)
+    if s.ndim == 1 and s.size in (2, 3):                # (H, W) or (H, W, 3): every frame
+        s = np.broadcast_to(s[:2], (n, 2))
+    elif s.ndim == 1 and s.size == 4:                   # a batch's (N, H, W, 3)
+        s = np.broadcast_to(s[1:3], (n, 2))
+    elif s.ndim == 2 and s.shape[1] >= 2 and len(s) >= n:
+        s = s[:, :2]
+    else:
+        raise ValueError('shapes must be (H, W), a batch shape (N, H, W, 3) or one (H, W) per frame, got %r' % (shapes,))
+    return s
+
+
+def pack_blur(faces_per_frame, shapes, radius=None, margin=0.0, shape='box'):
+    """-> lib.BLUR_DT array, faces in order, frame by frame: each face's bbox, widened by `margin` x its width left and
+    right and `margin` x its height top and bottom (Python floats), int()-truncated and clipped to its frame, as the
+    half-open region [x0, x1) x [y0, y1); a face whose region is empty is left out.  `shapes`: the frames' (H, W) --
+    one pair for all, a batch's shape (N, H, W, 3), or a pair per frame.  `radius`: GaussianBlur's, 0 .. 1024; None:
+    max(w, h) / 8 of the clipped region (at most 1024).  `shape`: 'box', or 'ellipse' (only the ellipse Pillow draws into the region is replaced).
+    Bad values raise ValueError before anything is blurred."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    if radius is not None and not 0 <= float(radius) <= BLUR_RADIUS_LIMIT:
+        raise ValueError('radius must be within 0 .. %g, got %r' % (BLUR_RADIUS_LIMIT, radius))
+    margin = float(margin)
+    if not math.isfinite(margin):
+        raise ValueError('margin must be finite, got %r' % (margin,))
+    sizes = _frame_sizes(shapes, len(faces_per_frame))
+    rows = []
+    for f, faces in enumerate(faces_per_frame):
+        h, w = int(sizes[f][0]), int(sizes[f][1])
+        for face in _as_list(faces):
+            x0, y0, x1, y1 = (float(v) for v in np.asarray(face['bbox']).reshape(4))
+            if margin:
+                dx, dy = margin * (x1 - x0), margin * (y1 - y0)
+                x0, y0, x1, y1 = x0 - dx, y0 - dy, x1 + dx, y1 + dy
+            if not all(abs(v) <= COORD_LIMIT for v in (x0, y0, x1, y1)):
+                raise ValueError('box coordinates must be finite and within +-2^24')
+            x0, y0, x1, y1 = max(int(x0), 0), max(int(y0), 0), min(int(x1), w), min(int(y1), h)
+            if x1 <= x0 or y1 <= y0:
+                continue
+            r = max(x1 - x0, y1 - y0) / 8 if radius is None else float(radius)
+            rows.append((f, x0, y0, x1, y1, BLUR_SHAPES[shape], min(r, BLUR_RADIUS_LIMIT)))
+    return np.array(rows, lib.BLUR_DT)
+
+
+def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ctx=None):
+    """Blur the faces of the resident batch `frames` (lib.Frames) in place: faces_per_frame[i] (a dict, or a list of dicts
+    as face_detection / face_tracking return) goes into frame i, in list order (a later face blurs what an earlier one it
+    overlaps left).  `radius`, `margin`, `shape`: pack_blur's.  `ctx`: the caller's context (default: the batch's own)."""
+    _check_batch(frames, faces_per_frame)
+    frames.blur(pack_blur(faces_per_frame, frames.shape, radius, margin, shape), ctx=ctx)
+    return frames
+
+
+def anonymize_faces(image, faces, radius=None, margin=0.0, shape='box'):
+    """A copy of the host image (uint8 (H, W, 3)) with every face (dict or list of dicts, face_tracking's included)
+    blurred: Pillow's crop / GaussianBlur(radius) / paste of each box."""
+    image = np.asarray(image)
+    return _on_host_image(image, pack_blur([faces], image.shape[:2], radius, margin, shape), blur=True)
+
+
+def _on_host_image(image, prims, masks=None, device=None, blur=False):
     from . import runtime
     image = np.asarray(image)
     if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
@@ -344,7 +417,10 @@ def _on_host_image(image, prims, masks=None, device=None):
     ctx = runtime.get_context(device)
     frames = ctx.upload(image[None])
     try:
-        frames.draw(prims, masks)
+        if blur:
+            frames.blur(prims)
+        else:
+            frames.draw(prims, masks)
         return frames.download()[0]
     finally:
         frames.free()
