@@ -8,7 +8,7 @@ Terran checkpoint (`torch.load(.pth)` -> dict of tensors) can be packed directly
 * ArcFace IR-ResNet100 reference: terran/face/recognition/arcface/model.py:4-97
 * OpenPose body 2017   reference: terran/pose/openpose/model.py:27-141
 
-Nothing here executes a network; `oracle/nets.py` (CPU) and `terran_amd/pack.py`
+Nothing here executes a network; `oracle/nets.py` (CPU) and `terran_amd/pack/`
 (HIP op-program builder) both walk these tables.
 """
 

@@ -3,7 +3,7 @@
     python tests/probe_map_error.py [wild|benign] [frames]
 Where the decision flips of tests/test_gpu_decisions_vs_oracle.py come from: how far each device mode's PAF / heat maps
 (and the torch-CPU float32 oracle's) are from the float64 maps, relative to the maps' RMS.  Pack-time knobs can be
-varied through the environment for experiments (a probe under tests/: it calls the oracle, which only tests may): TA_CH_SPREAD, TA_ACT_TARGET_LOG2 (terran_amd/pack.py)."""
+varied through the environment for experiments (a probe under tests/: it calls the oracle, which only tests may): TA_CH_SPREAD, TA_ACT_TARGET_LOG2 (terran_amd/pack/moments.py)."""
 import os
 import sys
 
@@ -12,12 +12,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from terran_amd import lib, pack, runtime, synth, weights   # noqa: E402
+from terran_amd.pack import moments                         # noqa: E402  (the module that READS the two knobs)
 from oracle import nets                                     # noqa: E402  (checker only)
 
 if os.environ.get('TA_CH_SPREAD'):
-    pack._CH_SPREAD = int(os.environ['TA_CH_SPREAD'])
+    moments._CH_SPREAD = int(os.environ['TA_CH_SPREAD'])
 if os.environ.get('TA_ACT_TARGET_LOG2'):
-    pack._ACT_TARGET_LOG2 = int(os.environ['TA_ACT_TARGET_LOG2'])
+    moments._ACT_TARGET_LOG2 = int(os.environ['TA_ACT_TARGET_LOG2'])
 
 
 def main():
@@ -40,7 +41,7 @@ def main():
         d = got.astype(np.float64) - ref
         print('%-22s rms err / rms(ref) %.3g   max err / rms(ref) %.3g' % (name, np.sqrt((d * d).mean()) / rms, np.abs(d).max() / rms))
     print('%s weights, %d frames 184 x 327, rms of the float64 maps %.4g; spread %d, target 2^%d' %
-          (kind, n, rms, pack._CH_SPREAD, pack._ACT_TARGET_LOG2))
+          (kind, n, rms, moments._CH_SPREAD, moments._ACT_TARGET_LOG2))
     row('torch-CPU float32', np.concatenate([p32, h32], 1))
     ctx = runtime.get_context(0)
     fr = ctx.upload(frames)

@@ -42,7 +42,7 @@ LAYERS = {
     'arc3x3_prelu': dict(n=64, h=28, w=28, c1=128, cout=128, k=3, act=2),
     # OpenPose VGG conv1_2 at the 1080p size: 3x3 64 -> 64 on 184 x 327 maps                           (model.py:41-57)
     'vgg3x3_64_c5': dict(n=8, h=184, w=327, c1=64, cout=64, k=3, act=1),
-    # conv + ReLU + 2x2 max-pool in one launch (pack.py `pool=True`; conv1_2 / conv2_2 / conv3_4 of the VGG front), odd sizes
+    # conv + ReLU + 2x2 max-pool in one launch (pack/program.py `pool=True`; conv1_2 / conv2_2 / conv3_4 of the VGG front), odd sizes
     'vgg3x3_64_pool_c5': dict(n=8, h=184, w=327, c1=64, cout=64, k=3, act=1, pool=True),
     'vgg3x3_128_pool_c5': dict(n=8, h=92, w=163, c1=128, cout=128, k=3, act=1, pool=True),
     'vgg3x3_256_pool_c5': dict(n=32, h=46, w=81, c1=256, cout=256, k=3, act=1, pool=True),
