@@ -261,6 +261,10 @@ int ta_jpeg_encode_last_opt_stats(const ta_ctx* ctx, double* ms);
  * (replaces load_model(): retinaface/wrapper.py:16-22, arcface/wrapper.py:13-19,
  * openpose/wrapper.py:27-36).  The blob is copied; the caller may free it. */
 int ta_model_load(ta_ctx* ctx, int kind, const void* blob, size_t bytes, ta_model** out);
+/* HOST ONLY, no context: every check of a blob that depends on the program alone -- header, tables, weight offsets, op
+ * records, tensor formats, data flow, lanes.  ta_model_load runs it first, so a program it accepts can only be refused
+ * later for the shape of an input or by the device.  TA_OK, or TA_E_INVALID with the defect in `msg` (may be NULL). */
+int ta_program_check(int kind, const void* blob, size_t bytes, char* msg, size_t msg_capacity);
 void ta_model_free(ta_model* m);
 int ta_model_kind(const ta_model* m);
 

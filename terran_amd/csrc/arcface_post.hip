@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256) void cosine_kernel(const float* a, int na, con
 
 static int embed_tail(ta_model* m, int n, int normalize, float* out) {
   ta_ctx* ctx = m->ctx;
-  const ta_tensor& E = m->tensors[m->hdr.outputs[0]];
+  const ta_tensor& E = m->tensor(m->hdr.outputs[0]);
   if (E.unscale_dev || E.fmt != 0) return ta_fail(ctx, TA_E_INVALID, "arcface: the embedding tensor must be plain float32");
   if (normalize) {
     ta_prof_scope scope(ctx, 3, (double)n * 512 * 8);
@@ -162,7 +162,7 @@ int ta_arcface_embed_faces_multi(ta_model* m, const ta_frames* const* frames, in
                        (const double*)(scr + aff_off), n, (uint8_t*)scr);
     TA_HIP(ctx, hipGetLastError());
   }
-  TA_TRY(ta_launch_preprocess(ctx, TA_PRE_ARCFACE_CROPS, (const uint8_t*)scr, n, 112, 112, m->tensors[m->hdr.input_tensor]));
+  TA_TRY(ta_launch_preprocess(ctx, TA_PRE_ARCFACE_CROPS, (const uint8_t*)scr, n, 112, 112, m->tensor(m->hdr.input_tensor)));
   TA_TRY(ta_model_run_ops(m));
   if (crops_out) TA_HIP(ctx, hipMemcpyAsync(crops_out, scr, crop_bytes, hipMemcpyDeviceToHost, ctx->stream));
   return embed_tail(m, n, normalize, out);

@@ -998,7 +998,7 @@ int ta_openpose_run(ta_model* m, const ta_frames* frames, double scale, int capa
   if (required) *required = 0;
   if (frames->n == 0) return TA_OK;
   TA_TRY(ta_model_forward_frames(m, frames));
-  const ta_tensor& X = m->tensors[m->hdr.outputs[0]];
+  const ta_tensor& X = m->tensor(m->hdr.outputs[0]);
   op_maps mp;
   mp.base = X.dev;
   mp.img = (int)((size_t)X.hp() * X.wp() * X.c);

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -13,7 +14,7 @@
 #include "../../include/terran_amd.h"
 
 // ---------------------------------------------------------------------------------------------
-// Packed model blob (written by terran_amd/pack.py, parsed by net.cpp).  All little-endian PODs.
+// Packed model blob (written by terran_amd/pack/, parsed and checked by model_load.hip).  All little-endian PODs.
 // ---------------------------------------------------------------------------------------------
 #define TA_BLOB_MAGIC 0x314D4154u /* "TAM1" */
 
@@ -82,6 +83,12 @@ struct ta_op_desc {
                                       // All ones outside the f16x3 / f16 programs
   double macs_per_pixel;              // algorithmic MACs per output pixel (true, unpadded dims)
 };
+
+// the fields of ta_op_desc::variant (the packer writes the bits; nothing else in C++ shifts or masks them)
+static inline int ta_op_forced_variant(const ta_op_desc& op) { return op.variant & 255; }
+static inline int ta_op_packed_ksplit(const ta_op_desc& op) { return (op.variant >> 8) & 255; }
+static inline bool ta_op_border_bias(const ta_op_desc& op) { return (op.variant >> 16) & 1; }
+static inline int ta_op_lane(const ta_op_desc& op) { return (op.variant >> 17) & 3; }
 
 static_assert(sizeof(ta_blob_header) == 128 && sizeof(ta_tensor_desc) == 20 && sizeof(ta_op_desc) == 152,
               "blob layout is shared with terran_amd/pack.py (HEADER_DT / TENSOR_DT / OP_DT)");
@@ -261,6 +268,9 @@ void ta_disc_rows(int a, int b, std::vector<int2>& tab);
 // ---------------------------------------------------------------------------------------------
 // Planned tensors / kernels
 // ---------------------------------------------------------------------------------------------
+// TA_FMT_F16 (act_format.h; that header is device code, this one is not): the one format with 2 bytes per element
+static inline bool ta_fmt_is_half(int fmt) { return fmt == 3; }
+
 struct ta_tensor {
   float* dev = nullptr;   // base of the padded allocation
   int n = 0, h = 0, w = 0, c = 0, halo = 0, fmt = 0;
@@ -270,10 +280,22 @@ struct ta_tensor {
   int hp() const { return h + 2 * halo; }
   int wp() const { return w + 2 * halo; }
   size_t elems() const { return (size_t)n * hp() * wp() * c; }            // allocation: 4 bytes per element in every format
-  int cf() const { return fmt == 3 /* TA_FMT_F16 */ ? c / 2 : c; }           // float slots per pixel (what strides are counted in)
+  int cf() const { return ta_fmt_is_half(fmt) ? c / 2 : c; }           // float slots per pixel (what strides are counted in)
   // element offset of interior pixel (img, y, x), channel 0
   size_t off(int img, int y, int x) const { return (((size_t)img * hp() + y + halo) * wp() + x + halo) * cf(); }
 };
+
+// The four strides a launch record keeps per tensor: slots per padded image / padded row / pixel, and the offset of the pixel
+// `pad` in front of the first interior one on both axes (an input read with that padding; 0 for an output, a residual, a
+// second output).  Slots are cf() for the convs; the dw+pw and depthwise records count in `c`, which is the same number
+// for them: only the half-float format halves the slots, and the loader keeps every op but the convs off such tensors.
+struct ta_strides {
+  int img, row, pix, off0;
+};
+static inline ta_strides ta_tensor_strides(const ta_tensor& t, int pad, bool count_c) {
+  const int s = count_c ? t.c : t.cf(), sh = t.halo - pad;
+  return {(int)((size_t)t.hp() * t.wp() * s), t.wp() * s, s, (int)(((size_t)sh * t.wp() + sh) * s)};
+}
 
 struct ta_conv_launch {
   const float* in;
@@ -343,6 +365,25 @@ static inline int ta_conv_ksplit(int coutp, int n_slabs, bool eligible, int pack
   return 32;
 }
 
+// How conv `op` walks K when its input tensor has format `in_fmt`: channels per K slab -- 32 (float32 and the hi | lo
+// formats: 128 bytes per pixel and slab), 64 in TA_FMT_F16 --, whether the slabs walk (channel block, kx, ky) without a
+// table, and the channel blocks per tap.  One rule for the program check, the planner and the executor.
+struct ta_k_geometry {
+  int kblk;
+  bool uniform;
+  int cblocks;
+};
+static inline ta_k_geometry ta_conv_k_geometry(const ta_op_desc& op, int in_fmt) {
+  const int kblk = ta_fmt_is_half(in_fmt) ? 64 : 32;
+  return {kblk, op.cin % kblk == 0 && op.n_slabs == (int64_t)op.kh * op.kw * (op.cin / kblk), op.cin / kblk};
+}
+// The K-split factor of conv `op` (1 = none).  It may be split when it runs on the split-role kernel (uniform K walk; f32
+// operands in f32 mode, pre-split operands in the half modes) and its epilogue is plain (dense, no fused pool).
+static inline int ta_op_ksplit(const ta_op_desc& op, int in_fmt) {
+  const bool eligible = ta_conv_k_geometry(op, in_fmt).uniform && in_fmt == ta_split_fmt_of(op.prec) && op.groups <= 1 && !op.pool;
+  return ta_conv_ksplit(op.coutp, op.n_slabs, eligible, ta_op_packed_ksplit(op));
+}
+
 int ta_launch_conv(ta_ctx* ctx, const ta_conv_launch& p, double flops);   // conv_igemm.hip: checks, kernel choice, then one of:
 // the kernel families, one translation unit each: `variant` is a TA_CV_* of that family that can run the launch
 // (variant_eligible), the arithmetic mode is p.prec; each does the switch to its template instances
@@ -380,9 +421,9 @@ int ta_launch_preprocess(ta_ctx* ctx, int mode, const uint8_t* src_dev, int n, i
 // ---------------------------------------------------------------------------------------------
 // Model
 // ---------------------------------------------------------------------------------------------
-// One activation plan = everything that depends on the input shape (N, H, W).
+// One activation plan = everything that depends on the input shape (N, H, W).  It owns its device memory.
 struct ta_plan {
-  int n = 0, h = 0, w = 0;
+  int n = 0, h = 0, w = 0;            // n = CAPACITY (>= ta_model::run_n)
   std::vector<ta_tensor> tensors;
   char* arena = nullptr;
   size_t arena_bytes = 0;
@@ -390,33 +431,45 @@ struct ta_plan {
   std::vector<size_t> ktab_off;   // per op, element offset into ktab_dev
   float* splitk_ws = nullptr;     // workspace for K-split partial sums (inside the arena)
   uint64_t last_use = 0;
+  ta_plan() = default;
+  ta_plan(const ta_plan&) = delete;
+  ~ta_plan() {
+    if (arena) (void)hipFree(arena);
+    if (ktab_dev) (void)hipFree(ktab_dev);
+  }
 };
 
-struct ta_model {
-  ta_ctx* ctx = nullptr;
-  int kind = 0;
+// What a blob says, on the host: filled and checked by ta_program_parse (model_load.hip), never changed afterwards.
+struct ta_program {
   ta_blob_header hdr;
   std::vector<ta_tensor_desc> tdesc;
   std::vector<ta_op_desc> ops;
+};
+// Every check that depends on the program alone (no context, no HIP call): TA_OK, or TA_E_INVALID with the defect in `msg`.
+int ta_program_parse(int kind, const void* blob, size_t bytes, ta_program* out, char* msg, size_t msg_capacity);
+
+struct ta_model : ta_program {
+  ta_ctx* ctx = nullptr;
+  int kind = 0;
   char* weights_dev = nullptr;
   bool has_half_ops = false;                    // any conv / dw+pw op with prec 3 / 4 / 5: every store is range-checked (ta_conv_launch::range_check)
   bool amax_on = false;                         // tools (ta_model_debug_amax): ops report the largest |x| they store into the context's slots
   std::vector<char> tensor_read;                // per tensor: some op of the program reads it (results no op reads are not range-checked)
   std::vector<std::vector<float>> unscale_host; // per tensor: host copy of its un-scale vector (empty: none)
   std::vector<char> weights_host_small;         // host copy of the few weights that travel as kernel arguments (TA_OP_RFSTEM)
-  // small LRU of plans (lists of differently-sized images alternate between a few shapes); `tensors`,
-  // `ktab_dev`, `ktab_off` mirror the active plan
-  std::vector<ta_plan*> plans;
+  // small LRU of plans (lists of differently-sized images alternate between a few shapes); `active` is the only link to the
+  // plan of the last successful ta_model_plan (nullptr: never planned, or evicted and the plan that followed failed)
+  std::vector<std::unique_ptr<ta_plan>> plans;
   ta_plan* active = nullptr;
   uint64_t use_counter = 0;
-  int plan_n = 0, plan_h = 0, plan_w = 0;      // plan_n = CAPACITY of the active plan (>= run_n)
-  int run_n = 0;                                // images / crops of the current call: every launch covers run_n, not plan_n
+  int run_n = 0;                                // images / crops of the current call: every launch covers run_n, not the plan's capacity
   const uint8_t* input_u8 = nullptr;            // the frames of the current forward_frames call (TA_OP_RFSTEM reads them)
-  std::vector<ta_tensor> tensors;
-  int32_t* ktab_dev = nullptr;
-  std::vector<size_t> ktab_off;
-  float* splitk_ws = nullptr;
+  const ta_tensor& tensor(int i) const { return active->tensors[i]; }
+  ~ta_model() {
+    plans.clear();
+    if (weights_dev) (void)hipFree(weights_dev);
+  }
 };
 
-int ta_model_plan(ta_model* m, int n, int h, int w);
-int ta_model_run_ops(ta_model* m);
+int ta_model_plan(ta_model* m, int n, int h, int w);   // model_plan.hip: makes the plan of (n, h, w) the active one, then sets run_n
+int ta_model_run_ops(ta_model* m);                     // model_run.hip: the op program on the active plan

@@ -64,6 +64,7 @@ SIGNATURES = {
     'ta_jpeg_encode_opt': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, P(c_void_p), P(c_size_t)]),
     'ta_jpeg_optimal_table': (c_int, [c_void_p, c_void_p, c_void_p, P(c_int)]),
     'ta_jpeg_encode_last_opt_stats': (c_int, [c_void_p, c_void_p]),
+    'ta_program_check': (c_int, [c_int, c_void_p, c_size_t, C.c_char_p, c_size_t]),
     'ta_model_load': (c_int, [c_void_p, c_int, c_void_p, c_size_t, P(c_void_p)]),
     'ta_model_free': (None, [c_void_p]),
     'ta_model_kind': (c_int, [c_void_p]),
@@ -179,6 +180,22 @@ def jpeg_optimal_table(freq):
     if rc != OK:
         raise TerranAmdError(rc, 'jpeg_optimal_table: frequencies must be 0 .. 10^9 - 1 and not all zero')
     return bits[1:].tolist(), vals[:n.value].tolist()
+
+
+def check_program(program_or_blob, kind=None):
+    """Host only (no context, no device): ta_program_check on a pack.Program or on the bytes of a blob (then `kind` is
+    needed) -- what ta_model_load refuses before it touches the device.  Raises TerranAmdError(TA_E_INVALID) with the defect."""
+    lib = load()
+    if isinstance(program_or_blob, (bytes, bytearray, memoryview)):
+        blob = bytes(program_or_blob)
+        if kind is None:
+            raise ValueError('check_program: the bytes of a blob need `kind` (a pack.MODEL_* constant)')
+    else:
+        blob, kind = program_or_blob.blob(), program_or_blob.kind if kind is None else kind
+    err = C.create_string_buffer(256)
+    rc = lib.ta_program_check(int(kind), blob, len(blob), err, len(err))
+    if rc != OK:
+        raise TerranAmdError(rc, err.value.decode(errors='replace'))
 
 
 def check_jpeg_options(quality, subsampling):

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 from terran_amd import pack, synth
+from tests.util import conv_case_program, dwpw_block_program, fc_program, pinned_variant_program, window_program, window_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -90,15 +91,6 @@ CASES = [
 _ref_cache = {}
 
 
-def _weights(L, rng):
-    c1, cout, k, groups = L['c1'], L['cout'], L['k'], L.get('groups', 1)
-    W1 = rng.normal(0, 0.3, (c1, 3, 3, 3)).astype(np.float32)
-    b1 = rng.normal(0, 0.1, c1).astype(np.float32)
-    W2 = rng.normal(0, 1.0 / np.sqrt(c1 // groups * k * k), (cout, c1 // groups, k, k)).astype(np.float32)
-    b2 = rng.normal(0, 0.1, cout).astype(np.float32)
-    return W1, b1, W2, b2
-
-
 @pytest.mark.parametrize('precision', ['f32', 'f16x3', 'bf16x3'])
 @pytest.mark.parametrize('layer,variant,mid_f32', CASES, ids=['%s-%s%s' % (a, b, '-f32in' if c else '') for a, b, c in CASES])
 def test_conv_variant_at_bench_size(ctx, layer, variant, mid_f32, precision):
@@ -121,37 +113,11 @@ def test_conv_variant_split_format_tensors(ctx, layer, variant, precision):
 def _run_case(ctx, layer, variant, mid_f32, precision, split_io):
     from terran_amd import lib
     L = LAYERS[layer]
-    rng = np.random.default_rng(11)
-    n, h, w, c1, cout, k = L['n'], L['h'], L['w'], L['c1'], L['cout'], L['k']
+    n, h, w, cout, k = L['n'], L['h'], L['w'], L['cout'], L['k']
     stride, groups, act = L.get('stride', 1), L.get('groups', 1), L.get('act', 0)
     out_off, out_total = L.get('out_off', 0), L.get('out_total', cout)
-    W1, b1, W2, b2 = _weights(L, rng)
-    P = pack.Program(pack.MODEL_OPENPOSE, precision)
-    t0 = P.tensor(4, 1)
-    P.input_tensor = t0
-    t1 = P.tensor(c1, k // 2, name='mid', f32=mid_f32)
-    P.conv(t0, t1, W1, b1, act=pack.ACT_RELU)
-    t2 = P.tensor(out_total, 0, name='out', f32=not split_io)
-    kw = dict(variant=lib.CONV_VARIANTS[variant], groups=groups)
-    prelu = scale2 = shift2 = Wr = br = None
-    if act == 2:
-        prelu = rng.uniform(0.1, 0.4, cout).astype(np.float32)
-        kw['prelu'] = prelu
-    if L.get('res'):
-        tres = P.tensor(cout, 0, name='res', f32=not split_io)
-        Wr = rng.normal(0, 0.3, (cout, 3, 3, 3)).astype(np.float32)
-        br = rng.normal(0, 0.1, cout).astype(np.float32)
-        P.conv(t0, tres, Wr, br, stride=stride, pad=1)
-        kw['res'] = tres
-    if L.get('out2'):
-        t3 = P.tensor(cout, 1, name='out2', f32=not split_io)
-        scale2 = rng.uniform(0.5, 1.5, cout).astype(np.float32)
-        shift2 = rng.normal(0, 0.2, cout).astype(np.float32)
-        kw.update(out2=t3, scale2=scale2, shift2=shift2)
-    if L.get('pool'):
-        kw['pool'] = True
-    P.conv(t1, t2, W2, b2, stride=stride, act=act, out_ch_off=out_off, cout_p=L.get('cout_p'), **kw)
-    P.outputs = [t2]
+    P, wts = conv_case_program(L, lib.CONV_VARIANTS[variant], mid_f32, precision, split_io)
+    W2, b2, prelu, scale2, shift2 = (wts[k_] for k_ in ('W2', 'b2', 'prelu', 'scale2', 'shift2'))
     m = lib.Model(ctx, P)
     images = synth.frames(5, n, h, w)
     fr = ctx.upload(images)
@@ -204,23 +170,8 @@ def test_fc_25088_to_512_at_c3_size(ctx, variant, precision):
     """ArcFace's Flatten + Linear 25088 -> 512 (arcface/model.py:79-85) as the 1x1 conv over the (N,1,1,25088) view, 256
     crops: the K-split path (32 fixed K ranges + ordered reduction) under `auto` / split variants, one pass under pipe64."""
     from terran_amd import lib
-    rng = np.random.default_rng(12)
     n = 256
-    P = pack.Program(pack.MODEL_OPENPOSE, precision)
-    t0 = P.tensor(4, 1)
-    P.input_tensor = t0
-    Z = P.tensor(512, 0, name='z')
-    W1 = rng.normal(0, 0.3, (512, 3, 3, 3)).astype(np.float32)
-    b1 = rng.normal(0, 0.1, 512).astype(np.float32)
-    P.conv(t0, Z, W1, b1, act=pack.ACT_RELU)
-    A = P.tensor(7 * 7 * 512, 0, alias_of=Z)
-    Wl = rng.normal(0, 1.0 / np.sqrt(25088), (512, 25088)).astype(np.float32)
-    bl = rng.normal(0, 0.1, 512).astype(np.float32)
-    f = np.arange(7 * 7 * 512)
-    ch_pos = (f % 49) * 512 + f // 49                               # (C,H,W) flatten order -> NHWC position
-    E = P.tensor(512, 0, name='emb', f32=True)
-    P.conv(A, E, Wl.reshape(512, 25088, 1, 1), bl, ch_pos=ch_pos, pad=0, variant=lib.CONV_VARIANTS[variant])
-    P.outputs = [E]
+    P, Wl, bl = fc_program(lib.CONV_VARIANTS[variant], precision)
     m = lib.Model(ctx, P)
     fr = ctx.upload(synth.frames(6, n, 7, 7))
     ctx.conv_counts(reset=True)
@@ -243,14 +194,7 @@ def test_fc_25088_to_512_at_c3_size(ctx, variant, precision):
 
 def test_pinned_variant_that_cannot_run_the_layer_is_an_error(ctx):
     from terran_amd import lib
-    rng = np.random.default_rng(1)
-    P = pack.Program(pack.MODEL_OPENPOSE, 'f32')
-    t0 = P.tensor(4, 1)
-    P.input_tensor = t0
-    t1 = P.tensor(16, 0, name='out')
-    P.conv(t0, t1, rng.normal(0, 0.3, (16, 3, 3, 3)).astype(np.float32), np.zeros(16, np.float32),
-           variant=lib.CONV_VARIANTS['split_2x4'])                  # Cin = 4: only the table-driven kernel can
-    P.outputs = [t1]
+    P = pinned_variant_program(lib.CONV_VARIANTS['split_2x4'])      # Cin = 4: only the table-driven kernel can
     m = lib.Model(ctx, P)
     with pytest.raises(lib.TerranAmdError) as e:
         m.forward_frames(ctx.upload(synth.frames(1, 1, 16, 16)))
@@ -286,31 +230,12 @@ def test_window_kernel_equals_streaming_kernel(ctx, layer, tile, precision):
     tests above hold against torch).  Also: the automatic choice takes the window kernel wherever it is eligible."""
     from terran_amd import lib
     L = WIN_LAYERS[layer]
-    rng = np.random.default_rng(23)
-    n, h, w, c1, cout, k = L['n'], L['h'], L['w'], L['c1'], L['cout'], L['k']
-    W1, b1, W2, b2 = _weights(L, rng)
-    prelu = rng.uniform(0.1, 0.4, cout).astype(np.float32)
-    Wr, br = rng.normal(0, 0.3, (cout, 3, 3, 3)).astype(np.float32), rng.normal(0, 0.1, cout).astype(np.float32)
+    n, h, w = L['n'], L['h'], L['w']
+    wts = window_weights(L)
     fr = ctx.upload(synth.frames(6, n, h, w))
     outs = {}
     for variant in ('split_' + tile, 'win_' + tile, 'auto'):
-        P = pack.Program(pack.MODEL_OPENPOSE, precision)
-        t0 = P.tensor(4, 1)
-        P.input_tensor = t0
-        t1 = P.tensor(c1, k // 2, name='mid')
-        P.conv(t0, t1, W1, b1, act=pack.ACT_RELU)
-        t2 = P.tensor(cout, 1, name='out')                       # split format (a conv reads it), halo 1
-        kw = dict(variant=lib.CONV_VARIANTS[variant], groups=L.get('groups', 1), act=L.get('act', 0))
-        if L.get('act') == 2:
-            kw['prelu'] = prelu
-        if L.get('res'):
-            tres = P.tensor(cout, 0, name='res')
-            P.conv(t0, tres, Wr, br, pad=1)
-            kw['res'] = tres
-        P.conv(t1, t2, W2, b2, **kw)
-        t3 = P.tensor(32, 0, name='sink', f32=True)              # keeps `out` in the split format
-        P.conv(t2, t3, rng.normal(0, 0.05, (32, cout, 3, 3)).astype(np.float32), np.zeros(32, np.float32))
-        P.outputs = [t3]
+        P = window_program(L, lib.CONV_VARIANTS[variant], precision, wts)
         m = lib.Model(ctx, P)
         ctx.conv_counts(reset=True)
         m.forward_frames(fr)
@@ -330,29 +255,6 @@ def test_window_kernel_equals_streaming_kernel(ctx, layer, tile, precision):
 
 
 # ---- the detector's [depthwise 3x3 -> 1x1] block: rf_dwpw_kernel (written for this block) against conv_dwpw (generic tiles) ----------
-def _dwpw_block_program(C, cout, stride, split_out):
-    """frames -> conv 3x3 (4 -> C, exact f32) -> [dw3x3 (stride) -> 1x1 C -> cout] (f16x3) [-> 1x1 conv (f16x3): the block's output is then
-    stored pre-split] -> float32 out."""
-    rng = np.random.default_rng(1000 * C + 10 * cout + stride)
-    P = pack.Program(pack.MODEL_OPENPOSE, 'f16x3')
-    t0 = P.tensor(4, 1)
-    P.input_tensor = t0
-    P.input_stats = (np.array([-0.05] * 3 + [0.0]), np.array([0.08] * 3 + [0.0]))
-    t1 = P.tensor(C, 1)
-    P.conv(t0, t1, rng.normal(0, 0.3, (C, 3, 3, 3)).astype(np.float32), rng.normal(0, 0.1, C).astype(np.float32), act=pack.ACT_RELU, precision='f32')
-    t2 = P.tensor(cout, 0, name='block', f32=not split_out)
-    P.dwpw(t1, t2, rng.normal(0, 0.3, (C, 1, 3, 3)).astype(np.float32), rng.normal(0, 0.1, C).astype(np.float32),
-           rng.normal(0, 2.0 / np.sqrt(C), (cout, C, 1, 1)).astype(np.float32), rng.normal(0, 0.1, cout).astype(np.float32),
-           stride=stride, precision='f16x3')
-    if split_out:
-        t3 = P.tensor(32, 0, name='out', f32=True)
-        P.conv(t2, t3, rng.normal(0, 0.05, (32, cout, 1, 1)).astype(np.float32), np.zeros(32, np.float32), precision='f16x3')
-        P.outputs = [t3]
-    else:
-        P.outputs = [t2]
-    return P
-
-
 @pytest.mark.parametrize('C,cout,stride,split_out', [(64, 64, 1, False), (64, 128, 2, False), (128, 128, 1, False), (128, 256, 2, False),
                                                      (256, 256, 1, True), (32, 32, 1, False), (32, 64, 2, False), (96, 40, 1, False),
                                                      (128, 128, 1, True), (64, 24, 1, False)])
@@ -361,7 +263,7 @@ def test_rf_dwpw_kernel_equals_the_generic_kernel(ctx, monkeypatch, C, cout, str
     do not fill their tiles (13 x 24, 5 x 3), across image boundaries (tiles of 64 / 128 raster-consecutive pixels), with cout
     tiles of 32 / 64 / 128 and partial ones (40, 24), stride 1 and 2, float32 and pre-split outputs."""
     from terran_amd import lib
-    prog = _dwpw_block_program(C, cout, stride, split_out)
+    prog = dwpw_block_program(C, cout, stride, split_out)
     tap = 'out' if split_out else 'block'
     for n, h, w in ((3, 13, 24), (2, 5, 3), (1, 40, 40), (5, 20, 20)):
         frames = ctx.upload(synth.frames(7 + n, n, h, w))

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.util import golden
+from tests.util import golden, lane_sharing_program, two_conv_program
 from terran_amd import pack, synth
 
 pytestmark = pytest.mark.gpu
@@ -116,20 +116,53 @@ def test_retinaface_lanes_equal_the_serial_program(ctx, states, monkeypatch):
 def test_lane_sharing_a_tensor_with_the_main_stream_is_refused(ctx):
     """The loader checks what makes lanes safe: an op outside a lane may not read what the lane writes."""
     from terran_amd import lib
-    rng = np.random.default_rng(5)
-    P = pack.Program(pack.MODEL_OPENPOSE, 'f32')
-    t0 = P.tensor(4, 1)
-    P.input_tensor = t0
-    t1, t2, t3 = P.tensor(32, 1), P.tensor(32, 1), P.tensor(32, 0)
-    w = lambda co, ci, k: rng.normal(0, 0.1, (co, ci, k, k)).astype(np.float32)
-    P.conv(t0, t1, w(32, 3, 3), np.zeros(32, np.float32))
-    P.lane = 1
-    P.conv(t1, t2, w(32, 32, 3), np.zeros(32, np.float32))
-    P.lane = 0
-    P.conv(t2, t3, w(32, 32, 1), np.zeros(32, np.float32))          # reads the lane's output on the main stream
-    P.outputs = [t3]
+    P = lane_sharing_program()
     with pytest.raises(lib.TerranAmdError):
         lib.Model(ctx, P)
+
+
+def test_model_without_a_plan_refuses_reads(ctx):
+    """A model points at its plan and at nothing else: before the first forward there is none, and the debug taps say so."""
+    from terran_amd import lib
+    m = lib.Model(ctx, two_conv_program())
+    n, c, h, w = (lib.c_int() for _ in range(4))
+    tid = m.names['out'][0]
+    assert ctx.lib.ta_model_tensor_shape(m.h, tid, lib.C.byref(n), lib.C.byref(c), lib.C.byref(h), lib.C.byref(w)) == lib.E_INVALID
+    with pytest.raises(lib.TerranAmdError) as e:
+        m.read('out')
+    assert e.value.code == lib.E_INVALID
+    m.forward_frames(ctx.upload(synth.frames(3, 2, 16, 16)))
+    assert m.read('out').shape == (2, 32, 14, 14)
+    assert ctx.lib.ta_model_tensor_shape(m.h, tid, lib.C.byref(n), lib.C.byref(c), lib.C.byref(h), lib.C.byref(w)) == lib.OK
+    assert (n.value, c.value, h.value, w.value) == (2, 32, 14, 14)
+    m.free()
+
+
+def test_failed_plan_leaves_the_model_as_it_was(ctx):
+    """A forward whose plan is refused (2 x 2 frames: the second conv has no output pixel) changes nothing the model shows:
+    the last good plan stays active with its own batch size, also when the plan cache is full and the refused call evicted
+    one of its plans first."""
+    from terran_amd import lib
+    m = lib.Model(ctx, two_conv_program())
+    good, small = ctx.upload(synth.frames(3, 2, 16, 16)), ctx.upload(synth.frames(4, 7, 2, 2))
+
+    def refused():
+        with pytest.raises(lib.TerranAmdError) as e:
+            m.forward_frames(small)
+        assert e.value.code == lib.E_INVALID and 'too small' in str(e.value)
+
+    m.forward_frames(good)
+    kept = m.read('out')
+    assert kept.shape == (2, 32, 14, 14) and np.abs(kept).max() > 0
+    refused()
+    assert np.array_equal(m.read('out'), kept)                     # n == 2: the shape is part of the comparison
+    for h in range(17, 22):                                         # five more shapes than the cache holds plans
+        m.forward_frames(ctx.upload(synth.frames(3, 2, h, 16)))
+        assert m.read('out').shape == (2, 32, h - 2, 14)
+    refused()
+    m.forward_frames(good)
+    assert np.array_equal(m.read('out'), kept)
+    m.free()
 
 
 @pytest.mark.parametrize('shape', [(1, 27, 123), (1, 29, 125), (2, 57, 249), (1, 5, 7), (1, 56, 248), (1, 31, 126), (3, 16, 16)],

@@ -95,11 +95,12 @@ def test_pads_match_reference_rule():
 
 
 def test_pack_programs_are_well_formed(states):
-    from terran_amd import pack
+    from terran_amd import lib, pack
     for kind, fn in (('openpose', pack.pack_openpose), ('arcface', pack.pack_arcface),
                      ('retinaface', pack.pack_retinaface)):
         P = fn(states(kind))
         blob = P.blob()
+        lib.check_program(P)                                        # what the loader refuses before it touches a device
         hdr = np.frombuffer(blob[:128], pack.HEADER_DT)[0]
         assert hdr['magic'] == pack.MAGIC and hdr['n_ops'] == len(P.ops)
         assert hdr['weights_off'] % 256 == 0 and hdr['weights_off'] + hdr['weights_bytes'] == len(blob)
@@ -408,7 +409,7 @@ def test_c_result_builder_yields_the_comprehensions_objects():
 
 def test_detector_lanes_are_closed_branches(monkeypatch):
     """pack.pack_retinaface marks the context module + heads of the stride-32 / 16 levels as lanes 1 / 2 (side streams,
-    ta_op_desc.variant bits 17..18).  What net.hip's loader enforces is checked here on the packed program too: a lane's ops
+    ta_op_desc.variant bits 17..18).  What model_load.hip's program check enforces is checked here on the packed program too: a lane's ops
     follow the op that finishes their input, write tensors nobody outside the lane touches, and read nothing that a later
     op outside the lane writes; TERRAN_AMD_NO_DETECTOR_LANES packs the same ops without lanes."""
     from terran_amd import pack, weights
