@@ -166,6 +166,54 @@ int ta_frames_blur(ta_ctx* ctx, ta_frames* frames, const ta_blur_region* regions
  * regions here.  TA_E_INVALID: an empty or inverted box, an unknown shape, a bad radius. */
 int ta_blur_plan(const ta_blur_region* regions, int n, int32_t* rounds, float* box_radius, uint32_t* weights);
 
+/* ---- resampling regions (face chips, resizing, pixelation) -------------------------------- */
+/* Pillow's Image.resize(size, filter, box=) on uint8 RGB, bit for bit (libImaging ImagingResample: two passes of 2^22
+ * fixed-point convolution, the horizontal one first and rounded to uint8; NEAREST: the affine scaler, whose source
+ * coordinate starts at b0 + step / 2 and is advanced by adding step = (b1 - b0) / out).  The filter codes are Pillow's. */
+#define TA_RESAMPLE_NEAREST 0
+#define TA_RESAMPLE_LANCZOS 1
+#define TA_RESAMPLE_BILINEAR 2
+#define TA_RESAMPLE_BICUBIC 3
+#define TA_RESAMPLE_BOX 4
+#define TA_RESAMPLE_HAMMING 5
+typedef struct ta_resample_region {
+  int32_t frame;         /* image index in the batch                  */
+  float x0, y0, x1, y1;  /* Pillow's box=: fractional source rectangle */
+} ta_resample_region;
+/* *out: a NEW batch (n, out_h, out_w, 3), owned by `ctx`; image i is
+ *     Image.fromarray(src[regions[i].frame]).resize((out_w, out_h), filter, box=regions[i] box)
+ * Regions may name the frames in any order and any frame any number of times.  One horizontal and one vertical launch
+ * serve all regions; a pass is skipped for a region where Pillow skips it (same size and the box over the whole axis).
+ * The horizontal results (only the source rows the vertical pass reads) live in the context's scratch.  Returns when done.
+ * n = 0: TA_OK and *out = NULL.  TA_E_INVALID, before any launch (*out = NULL): n < 0; unknown filter; out_h or out_w
+ * outside 1 .. 16384; a frame index out of range; a box that is not 0 <= x0 < x1 <= W, 0 <= y0 < y1 <= H (Pillow's rule). */
+int ta_frames_resample(ta_ctx* ctx, const ta_frames* src, const ta_resample_region* regions, int n, int out_h, int out_w,
+                       int filter, ta_frames** out);
+/* HOST ONLY, no context: one axis' tables exactly as ta_frames_resample derives them for an axis it does not skip.
+ * bounds[2 i], bounds[2 i + 1]: first source sample and number of taps of output sample i; coefs[i * *ksize + t]: the
+ * 2^22 fixed-point weight of tap t (0 beyond the count).  NEAREST: one tap of weight 2^22.  b0, b1 are rounded to
+ * float32 first (the box is float32 in Pillow).  *ksize is set whenever the arguments are valid; TA_E_CAPACITY when
+ * out_size * *ksize > capacity (nothing else written: call with capacity 0 to size the arrays).  TA_E_INVALID:
+ * in_size <= 0, out_size outside 1 .. 16384, unknown filter, a box that is not 0 <= b0 < b1 <= in_size, a null pointer. */
+int ta_resample_plan(int in_size, double b0, double b1, int out_size, int filter, int32_t* bounds, int32_t* coefs,
+                     int capacity, int* ksize);
+
+/* Pixelates rectangles of `frames` in place, Pillow's
+ *     w, h = box size; sw, sh = max(1, w // block), max(1, h // block)
+ *     im.paste(im.crop(box).resize((sw, sh), BOX).resize((w, h), NEAREST), box)
+ * bit for bit.  Regions are as ta_frames_blur takes them: a half-open box inside the frame, TA_BLUR_BOX or
+ * TA_BLUR_ELLIPSE (only the pixels of ImageDraw.ellipse([0, 0, w - 1, h - 1], fill=) are replaced), applied in list
+ * order where they overlap within a frame (rounds of pairwise disjoint regions, three launches per round).  block = 1
+ * leaves the region as it is.  n = 0: TA_OK.  TA_E_INVALID, before any pixel changes: as for ta_frames_blur, or a block
+ * outside 1 .. 16384. */
+typedef struct ta_pixelate_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  int32_t block;         /* side of a mosaic cell, in pixels          */
+} ta_pixelate_region;
+int ta_frames_pixelate(ta_ctx* ctx, ta_frames* frames, const ta_pixelate_region* regions, int n);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

@@ -17,6 +17,7 @@
 // after the first.  Every output of a pass depends only on the pass's input buffer, so the result does not depend on
 // the launch geometry.  The ellipse mask is TA_DRAW_DISC's span table (ta_disc_rows, draw.hip).
 #include "ta_internal.h"
+#include "region_rounds.h"
 
 #include <math.h>
 #include <string.h>
@@ -149,24 +150,6 @@ const char* check_region(const ta_blur_region& q) {
   return nullptr;
 }
 
-// A region runs one round after the latest round of an earlier region of its frame that it intersects.
-int plan_rounds(const ta_blur_region* regions, int n, std::vector<int32_t>& round) {
-  round.assign(n, 0);
-  std::map<int32_t, std::vector<int>> of_frame;
-  int rounds = 0;
-  for (int i = 0; i < n; ++i) {
-    const ta_blur_region& q = regions[i];
-    std::vector<int>& earlier = of_frame[q.frame];
-    for (int j : earlier) {
-      const ta_blur_region& e = regions[j];
-      if (q.x0 < e.x1 && e.x0 < q.x1 && q.y0 < e.y1 && e.y0 < q.y1) round[i] = std::max(round[i], round[j] + 1);
-    }
-    earlier.push_back(i);
-    rounds = std::max(rounds, round[i] + 1);
-  }
-  return rounds;
-}
-
 // What one call launches: the records of the regions that change something, round by round, the strips of both stages
 // of every round (one workgroup each), the ellipse span tables and the size of the pixel scratch (the largest round's).
 struct blur_launch {
@@ -183,7 +166,7 @@ struct blur_work {
 
 void plan_work(const ta_blur_region* regions, int n, blur_work& w) {
   std::vector<int32_t> round;
-  const int rounds = plan_rounds(regions, n, round);
+  const int rounds = ta_plan_rounds(regions, n, round);
   // records, strips and the pixel scratch, round by round (a radius of 0 changes nothing, as in Pillow: no record)
   std::vector<blur_rec>& recs = w.recs;
   std::vector<blur_item>& items = w.items;
@@ -248,7 +231,7 @@ extern "C" int ta_blur_plan(const ta_blur_region* regions, int n, int32_t* round
   for (int i = 0; i < n; ++i)
     if (check_region(regions[i])) return TA_E_INVALID;
   std::vector<int32_t> round;
-  plan_rounds(regions, n, round);
+  ta_plan_rounds(regions, n, round);
   for (int i = 0; i < n; ++i) {
     float fr;
     int32_t r;

@@ -21,6 +21,10 @@ them to files.  Pillow's argument semantics: quality 1..100 (default 75), subsam
 1 / '4:2:2', 2 / '4:2:0'; optimize=True codes every image with Huffman tables built from its own statistics
 (`ta_jpeg_encode_opt`: smaller files, the same pixels), again Pillow's bytes.  Other options (progressive, qtables, dpi,
 exif, ...) are not offered.
+
+`resize_frames(frames, size, resample, box)` resizes resident batches on the GPU (`ta_frames_resample`) with the pixels of
+Pillow's `Image.resize(size, resample, box=box)` bit for bit, for every Pillow filter, and always returns ONE batch, so a
+mixed-size list from `open_images` becomes a batch of a common size (for `encode_jpeg`, a video writer, a network).
 """
 import os
 from pathlib import Path
@@ -176,6 +180,63 @@ def _tag(frames, paths):
     for f, p in zip(frames, paths):
         f.decode_paths = np.array([p], np.int32)
     return frames
+
+
+def resize_frames(frames, size, resample='bicubic', box=None, ctx=None):
+    """Resident frames resized -> one NEW resident `lib.Frames` (sum(n), height, width, 3), images in input order, each
+    Pillow's `Image.fromarray(frame).resize(size, resample, box=box)`.  `frames`: a `lib.Frames` batch or a list of them
+    (as `open_images` returns for mixed sizes); `size`: (width, height), as in Pillow; `resample`: 'nearest', 'box',
+    'bilinear', 'hamming', 'bicubic', 'lanczos' or Pillow's integer code; `box`: Pillow's (x0, y0, x1, y1) source
+    rectangle, fractional, applied to every frame (None: the whole frame).  `ctx`: the context the work runs on and the
+    result belongs to (default: the first batch's own).  Every argument is checked before anything is launched."""
+    if isinstance(frames, lib.Frames):
+        batches = [frames]
+    elif isinstance(frames, (list, tuple)) and frames and all(isinstance(b, lib.Frames) for b in frames):
+        batches = list(frames)
+    else:
+        raise ValueError('resize_frames: a lib.Frames batch or a non-empty list of them')
+    code = lib.resample_filter(resample)
+    try:
+        width, height = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('resize_frames: size must be (width, height), got %r' % (size,)) from None
+    if not (1 <= width <= lib.RESAMPLE_SIDE_LIMIT and 1 <= height <= lib.RESAMPLE_SIDE_LIMIT):
+        raise ValueError('resize_frames: size must be within 1 .. %d a side, got %r' % (lib.RESAMPLE_SIDE_LIMIT, size))
+    if box is not None:
+        box = tuple(float(np.float32(v)) for v in box)          # Pillow reads the box as float32
+        if len(box) != 4:
+            raise ValueError('resize_frames: box must be (x0, y0, x1, y1), got %r' % (box,))
+    total = sum(b.shape[0] for b in batches)
+    if total == 0:
+        raise ValueError('resize_frames: no images')
+    for b in batches:
+        h, w = b.shape[1:3]
+        x0, y0, x1, y1 = box if box is not None else (0.0, 0.0, float(w), float(h))
+        if not (0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h):
+            raise ValueError('resize_frames: box %r must satisfy 0 <= x0 < x1 <= %d and 0 <= y0 < y1 <= %d' % (box, w, h))
+    ctx = ctx if ctx is not None else batches[0].ctx
+    parts = []
+    for b in batches:
+        n, h, w = b.shape[:3]
+        if not n:
+            continue
+        regions = np.zeros(n, lib.RESAMPLE_DT)
+        regions['frame'] = np.arange(n)
+        regions['x0'], regions['y0'], regions['x1'], regions['y1'] = box if box is not None else (0, 0, w, h)
+        parts.append(b.resample(regions, height, width, code, ctx=ctx))
+    if len(parts) == 1:
+        return parts[0]
+    try:
+        out = lib.Frames.zeros(ctx, total, height, width)
+        at = 0
+        for p in parts:
+            for k in range(p.shape[0]):
+                out.paste(p, k, at, 0, 0)
+                at += 1
+        ctx.sync()
+    finally:
+        _free(parts)
+    return out
 
 
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}

@@ -54,6 +54,9 @@ SIGNATURES = {
     'ta_frames_draw_masks': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_frames_blur': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_blur_plan': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'ta_frames_resample': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, P(c_void_p)]),
+    'ta_resample_plan': (c_int, [c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_int, P(c_int)]),
+    'ta_frames_pixelate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -121,6 +124,44 @@ def blur_plan(regions):
     if rc != OK:
         raise TerranAmdError(rc, 'blur_plan: an empty or inverted box, an unknown shape or a bad radius')
     return rounds, fr, w
+
+
+# ta_resample_region, ta_pixelate_region (include/terran_amd.h) and the filters TA_RESAMPLE_*: Pillow's codes
+NEAREST, LANCZOS, BILINEAR, BICUBIC, BOX, HAMMING = 0, 1, 2, 3, 4, 5
+RESAMPLE_FILTERS = {'nearest': NEAREST, 'lanczos': LANCZOS, 'bilinear': BILINEAR, 'bicubic': BICUBIC, 'box': BOX,
+                    'hamming': HAMMING}
+RESAMPLE_DT = np.dtype([('frame', '<i4'), ('x0', '<f4'), ('y0', '<f4'), ('x1', '<f4'), ('y1', '<f4')])
+assert RESAMPLE_DT.itemsize == 20
+PIXELATE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                        ('block', '<i4')])
+assert PIXELATE_DT.itemsize == 28
+RESAMPLE_SIDE_LIMIT = 16384                             # an output side, a pixelate block
+
+
+def resample_filter(resample):
+    """A filter's name ('nearest', 'lanczos', 'bilinear', 'bicubic', 'box', 'hamming') or Pillow's integer code -> the
+    code, or ValueError."""
+    if isinstance(resample, str) and resample.lower() in RESAMPLE_FILTERS:
+        return RESAMPLE_FILTERS[resample.lower()]
+    if isinstance(resample, (int, np.integer)) and not isinstance(resample, bool) and int(resample) in RESAMPLE_FILTERS.values():
+        return int(resample)
+    raise ValueError('resample must be one of %s or Pillow\'s code 0 .. 5, got %r' % (sorted(RESAMPLE_FILTERS), resample))
+
+
+def resample_plan(in_size, b0, b1, out_size, filter):
+    """Host only (no context, no device): ta_resample_plan -> (int32 (out_size, 2) bounds: first source sample and tap
+    count, int32 (out_size, ksize) coefficients, 2^22 = 1): one axis' tables as ta_frames_resample derives them."""
+    lib = load()
+    k = c_int()
+    rc = lib.ta_resample_plan(int(in_size), float(b0), float(b1), int(out_size), int(filter), None, None, 0, C.byref(k))
+    if rc != E_CAPACITY:
+        raise TerranAmdError(rc, 'resample_plan(%r, %r, %r, %r, %r)' % (in_size, b0, b1, out_size, filter))
+    bounds, coefs = np.zeros((out_size, 2), np.int32), np.zeros((out_size, k.value), np.int32)
+    rc = lib.ta_resample_plan(int(in_size), float(b0), float(b1), int(out_size), int(filter), ptr(bounds), ptr(coefs),
+                              coefs.size, C.byref(k))
+    if rc != OK:
+        raise TerranAmdError(rc, 'resample_plan(%r, %r, %r, %r, %r)' % (in_size, b0, b1, out_size, filter))
+    return bounds, coefs
 
 
 # ta_jpeg_header and the decode paths TA_JPEG_* (include/terran_amd.h)
@@ -525,6 +566,26 @@ class Frames:
         ctx = ctx or self.ctx
         regions = np.ascontiguousarray(regions, dtype=BLUR_DT)
         ctx.check(ctx.lib.ta_frames_blur(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+
+    def resample(self, regions, out_h, out_w, filter, ctx=None):
+        """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's resize((out_w, out_h), filter, box=) of the
+        frame and fractional box regions[i] names (a RESAMPLE_DT array; ta_frames_resample), or None without regions.
+        `filter`: a TA_RESAMPLE_* / Pillow code.  `ctx`: the context the work runs on and the result belongs to -- the
+        CALLER's, as in `resize`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=RESAMPLE_DT)
+        hd = c_void_p()
+        ctx.check(ctx.lib.ta_frames_resample(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), int(out_h),
+                                             int(out_w), int(filter), C.byref(hd)))
+        return Frames(ctx, handle=hd) if hd.value else None
+
+    def pixelate(self, regions, ctx=None):
+        """Pixelate `regions` (a PIXELATE_DT array, in order) of this batch in place (ta_frames_pixelate): each half-open box
+        shrunk by its `block` with Pillow's BOX filter and enlarged again with NEAREST, pasted back under its shape.
+        `ctx`: the context the work runs on -- the CALLER's, as in `draw`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=PIXELATE_DT)
+        ctx.check(ctx.lib.ta_frames_pixelate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
 
     def encode_jpeg(self, quality=75, subsampling=2, ctx=None, optimize=False):
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs

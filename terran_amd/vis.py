@@ -22,8 +22,13 @@ face's box, int()-truncated and clipped to the frame, is replaced by Pillow's
 `im.crop(box).filter(ImageFilter.GaussianBlur(radius))` bit for bit (csrc/blur.hip), optionally only under the ellipse
 `ImageDraw.ellipse` draws into that box, so a video job makes its faces unrecognisable without downloading a frame.
 
+With method='pixelate' the box becomes a mosaic instead (Pillow's resize to 1 / block with BOX and back with NEAREST;
+csrc/resample.hip).  `crop_faces` cuts the same boxes out of a resident batch as chips of one size, Pillow's
+`resize(size, resample, box=box)` bit for bit, into one new resident batch that `image.encode_jpeg` / `save_images`
+take as it is.
+
 Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch, the
-blurring one ta_frames_blur call.  Importing this module needs no GPU and no Pillow.
+blurring one ta_frames_blur or ta_frames_pixelate call, the cropping one ta_frames_resample call.  Importing this module needs no GPU and no Pillow.
 """
 import collections
 import math
@@ -371,14 +376,50 @@ def pack_blur(faces_per_frame, shapes, radius=None, margin=0.0, shape='box'):
         raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
     if radius is not None and not 0 <= float(radius) <= BLUR_RADIUS_LIMIT:
         raise ValueError('radius must be within 0 .. %g, got %r' % (BLUR_RADIUS_LIMIT, radius))
+    rows = []
+    for f, _, x0, y0, x1, y1 in _clipped_boxes(faces_per_frame, shapes, margin):
+        r = max(x1 - x0, y1 - y0) / 8 if radius is None else float(radius)
+        rows.append((f, x0, y0, x1, y1, BLUR_SHAPES[shape], min(r, BLUR_RADIUS_LIMIT)))
+    return np.array(rows, lib.BLUR_DT)
+
+
+def pack_pixelate(faces_per_frame, shapes, block=None, margin=0.0, shape='box'):
+    """-> lib.PIXELATE_DT array: pack_blur's regions (the same margin, truncation, clipping and order) with the side of a
+    mosaic cell in place of the radius.  `block`: an int 1 .. 16384; None: max(1, max(w, h) // 8) of the clipped region."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    if block is not None and (isinstance(block, bool) or not isinstance(block, (int, np.integer))
+                              or not 1 <= block <= lib.RESAMPLE_SIDE_LIMIT):
+        raise ValueError('block must be an int within 1 .. %d, got %r' % (lib.RESAMPLE_SIDE_LIMIT, block))
+    rows = []
+    for f, _, x0, y0, x1, y1 in _clipped_boxes(faces_per_frame, shapes, margin):
+        b = max(1, max(x1 - x0, y1 - y0) // 8) if block is None else int(block)
+        rows.append((f, x0, y0, x1, y1, BLUR_SHAPES[shape], min(b, lib.RESAMPLE_SIDE_LIMIT)))
+    return np.array(rows, lib.PIXELATE_DT)
+
+
+def pack_crops(faces_per_frame, shapes, margin=0.0):
+    """-> (lib.RESAMPLE_DT array, int32 (n, 2) index of (frame, face) pairs): pack_blur's regions (the same margin,
+    truncation, clipping and order) as the source boxes of Frames.resample; a face whose region is empty is left out of
+    both.  Host only."""
+    rows, index = [], []
+    for f, k, x0, y0, x1, y1 in _clipped_boxes(faces_per_frame, shapes, margin):
+        rows.append((f, x0, y0, x1, y1))
+        index.append((f, k))
+    return np.array(rows, lib.RESAMPLE_DT), np.array(index, np.int32).reshape(-1, 2)
+
+
+def _clipped_boxes(faces_per_frame, shapes, margin):
+    """[(frame, face, x0, y0, x1, y1)]: every face's bbox widened by `margin`, int()-truncated and clipped to its frame,
+    faces in order, frame by frame; empty ones left out."""
     margin = float(margin)
     if not math.isfinite(margin):
         raise ValueError('margin must be finite, got %r' % (margin,))
     sizes = _frame_sizes(shapes, len(faces_per_frame))
-    rows = []
+    out = []
     for f, faces in enumerate(faces_per_frame):
         h, w = int(sizes[f][0]), int(sizes[f][1])
-        for face in _as_list(faces):
+        for k, face in enumerate(_as_list(faces)):
             x0, y0, x1, y1 = (float(v) for v in np.asarray(face['bbox']).reshape(4))
             if margin:
                 dx, dy = margin * (x1 - x0), margin * (y1 - y0)
@@ -388,25 +429,73 @@ def pack_blur(faces_per_frame, shapes, radius=None, margin=0.0, shape='box'):
             x0, y0, x1, y1 = max(int(x0), 0), max(int(y0), 0), min(int(x1), w), min(int(y1), h)
             if x1 <= x0 or y1 <= y0:
                 continue
-            r = max(x1 - x0, y1 - y0) / 8 if radius is None else float(radius)
-            rows.append((f, x0, y0, x1, y1, BLUR_SHAPES[shape], min(r, BLUR_RADIUS_LIMIT)))
-    return np.array(rows, lib.BLUR_DT)
+            out.append((f, k, x0, y0, x1, y1))
+    return out
 
 
-def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ctx=None):
+def crop_faces(frames, faces_per_frame, size=(112, 112), margin=0.0, resample='bicubic', ctx=None):
+    """Cut the faces of the resident batch `frames` (lib.Frames) out as chips of one size -> (chips, index): `chips` one
+    resident (n_faces, height, width, 3) lib.Frames, faces in order, frame by frame (None when there is no face), each
+    Pillow's `Image.fromarray(frame).resize(size, resample, box=box)` of the face's box as pack_blur clips it; `index`
+    the int32 (n_faces, 2) (frame, face) pairs of the chips.  `size`: (width, height); `resample`: a filter's name or
+    Pillow's code.  `encode_jpeg` / `save_images` take `chips` as they are.  `ctx`: the caller's context."""
+    _check_batch(frames, faces_per_frame)
+    width, height = _chip_size(size)
+    code = lib.resample_filter(resample)
+    regions, index = pack_crops(faces_per_frame, frames.shape, margin)
+    if not len(regions):
+        return None, index
+    return frames.resample(regions, height, width, code, ctx=ctx), index
+
+
+def _chip_size(size):
+    try:
+        width, height = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('size must be (width, height), got %r' % (size,)) from None
+    if not (1 <= width <= lib.RESAMPLE_SIDE_LIMIT and 1 <= height <= lib.RESAMPLE_SIDE_LIMIT):
+        raise ValueError('size must be within 1 .. %d a side, got %r' % (lib.RESAMPLE_SIDE_LIMIT, size))
+    return width, height
+
+
+BLUR_METHODS = ('gaussian', 'pixelate')
+
+
+def _pack_anonymize(faces_per_frame, shapes, radius, margin, shape, method, block):
+    """-> (regions, pixelate?) for blur_faces / anonymize_faces; every argument is checked before anything is launched."""
+    if method not in BLUR_METHODS:
+        raise ValueError("method must be 'gaussian' or 'pixelate', got %r" % (method,))
+    if method == 'pixelate':
+        if radius is not None:
+            raise ValueError("radius belongs to method='gaussian'; method='pixelate' takes block")
+        return pack_pixelate(faces_per_frame, shapes, block, margin, shape), True
+    if block is not None:
+        raise ValueError("block belongs to method='pixelate'; method='gaussian' takes radius")
+    return pack_blur(faces_per_frame, shapes, radius, margin, shape), False
+
+
+def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ctx=None, method='gaussian', block=None):
     """Blur the faces of the resident batch `frames` (lib.Frames) in place: faces_per_frame[i] (a dict, or a list of dicts
     as face_detection / face_tracking return) goes into frame i, in list order (a later face blurs what an earlier one it
-    overlaps left).  `radius`, `margin`, `shape`: pack_blur's.  `ctx`: the caller's context (default: the batch's own)."""
+    overlaps left).  `radius`, `margin`, `shape`: pack_blur's.  `ctx`: the caller's context (default: the batch's own).
+    `method`: 'gaussian', or 'pixelate' (a mosaic: Pillow's `region.resize(small, BOX).resize(region.size, NEAREST)` with
+    cells of `block` pixels, None: max(1, max(w, h) // 8) of each box; it takes no `radius`)."""
     _check_batch(frames, faces_per_frame)
-    frames.blur(pack_blur(faces_per_frame, frames.shape, radius, margin, shape), ctx=ctx)
+    regions, pixelate = _pack_anonymize(faces_per_frame, frames.shape, radius, margin, shape, method, block)
+    if pixelate:
+        frames.pixelate(regions, ctx=ctx)
+    else:
+        frames.blur(regions, ctx=ctx)
     return frames
 
 
-def anonymize_faces(image, faces, radius=None, margin=0.0, shape='box'):
+def anonymize_faces(image, faces, radius=None, margin=0.0, shape='box', method='gaussian', block=None):
     """A copy of the host image (uint8 (H, W, 3)) with every face (dict or list of dicts, face_tracking's included)
-    blurred: Pillow's crop / GaussianBlur(radius) / paste of each box."""
+    blurred: Pillow's crop / GaussianBlur(radius) / paste of each box, or with method='pixelate' its crop / resize(BOX) /
+    resize(NEAREST) / paste (`block`: blur_faces')."""
     image = np.asarray(image)
-    return _on_host_image(image, pack_blur([faces], image.shape[:2], radius, margin, shape), blur=True)
+    regions, pixelate = _pack_anonymize([faces], image.shape[:2], radius, margin, shape, method, block)
+    return _on_host_image(image, regions, blur='pixelate' if pixelate else True)
 
 
 def _on_host_image(image, prims, masks=None, device=None, blur=False):
@@ -417,7 +506,9 @@ def _on_host_image(image, prims, masks=None, device=None, blur=False):
     ctx = runtime.get_context(device)
     frames = ctx.upload(image[None])
     try:
-        if blur:
+        if blur == 'pixelate':
+            frames.pixelate(prims)
+        elif blur:
             frames.blur(prims)
         else:
             frames.draw(prims, masks)
