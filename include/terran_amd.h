@@ -214,6 +214,47 @@ typedef struct ta_pixelate_region {
 } ta_pixelate_region;
 int ta_frames_pixelate(ta_ctx* ctx, ta_frames* frames, const ta_pixelate_region* regions, int n);
 
+/* ---- transforming frames (rotation, flips, affine and perspective warps) ------------------- */
+/* Pillow's Image.transform(size, method, data, resample, fillcolor=) on uint8 RGB, bit for bit (libImaging Geometry.c).
+ * `a` is Pillow's `data`: it maps OUTPUT pixel centres to INPUT coordinates, in double without fused multiply-adds:
+ *     xin = x + 0.5, yin = y + 0.5;  xs = a0 xin + a1 yin + a2,  ys = a3 xin + a4 yin + a5
+ *     PERSPECTIVE: both divided by a6 xin + a7 yin + 1
+ * A pixel whose point fails 0 <= xs < W && 0 <= ys < H gets the fill colour.  BILINEAR / BICUBIC: 2 x 2 / 4 x 4 taps
+ * around (xs - 0.5, ys - 0.5), clipped to the image, interpolated in double, truncated (bicubic: clamped first).
+ * NEAREST takes Pillow's routes: an affine map with a1 == a3 == 0 its scaler (coordinates accumulated by adding a0, a4),
+ * another affine map 16.16 fixed point while its output corners stay below 32768 and accumulated doubles beyond (one
+ * thread per output row: slow, and of no practical use), PERSPECTIVE (int) of the double point.
+ * Where Pillow is undefined (it converts non-finite or out-of-range doubles to int: a perspective denominator of exactly 0
+ * at a pixel centre, NEAREST coordinates of 2^31 or more) the result here is defined and differs: every point is
+ * range-tested in double first and one that is not inside, NaN included, gets the fill colour. */
+#define TA_TRANSFORM_AFFINE 0      /* Pillow's Image.AFFINE      : a[0..5] (a[6], a[7] are not read) */
+#define TA_TRANSFORM_PERSPECTIVE 2 /* Pillow's Image.PERSPECTIVE : a[0..7] */
+typedef struct ta_transform_region {
+  int32_t frame;  /* image index in the batch */
+  int32_t method; /* TA_TRANSFORM_*           */
+  double a[8];    /* Pillow's `data`          */
+} ta_transform_region;
+/* *out: a NEW batch (n, out_h, out_w, 3), owned by `ctx`; image i is
+ *     Image.fromarray(src[r.frame]).transform((out_w, out_h), r.method, r.a, resample=filter, fillcolor=fill), r = regions[i]
+ * fill_rgb = NULL is fillcolor=None (zeros).  filter: TA_RESAMPLE_NEAREST, _BILINEAR or _BICUBIC.  Regions may name the
+ * frames in any order and any frame any number of times; one launch serves all of them (a second one only for NEAREST
+ * regions on the accumulated-double route).  Returns when done.
+ * n = 0: TA_OK and *out = NULL.  TA_E_INVALID, before any launch (*out = NULL): n < 0; another filter; out_h or out_w
+ * outside 1 .. 16384; a frame index out of range; an unknown method; a coefficient the method reads that is not finite. */
+int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_transform_region* regions, int n, int out_h, int out_w,
+                        int filter, const uint8_t* fill_rgb, ta_frames** out);
+/* Image.transpose(op) of every image of the batch into a NEW batch, owned by `ctx`: (n, h, w, 3) for the flips and
+ * ROTATE_180, (n, w, h, 3) for the four ops that swap the axes (ROTATE_90 is counter-clockwise, as in Pillow).  The op
+ * codes are Pillow's.  One launch, a tiled copy through LDS.  TA_E_INVALID (*out = NULL): an unknown op. */
+#define TA_FLIP_LEFT_RIGHT 0
+#define TA_FLIP_TOP_BOTTOM 1
+#define TA_ROTATE_90 2
+#define TA_ROTATE_180 3
+#define TA_ROTATE_270 4
+#define TA_TRANSPOSE 5
+#define TA_TRANSVERSE 6
+int ta_frames_transpose(ta_ctx* ctx, const ta_frames* src, int op, ta_frames** out);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

@@ -15,13 +15,16 @@ _TEMPLATE[:, 0] += 8.0
 _IDENTITY = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
 
 
-def align_matrices(landmarks):
+def align_matrices(landmarks, side=112):
     """(n,5,2) landmark sets -> (n,6) inverse 2x3 similarities (float64, PIL AFFINE convention) taking crop pixels to
     image coordinates: least-squares similarity landmarks -> template (Umeyama; closed form in 2-D, proper rotations
     only), inverted in closed form.  arcface/wrapper.py:50-61.  One vectorised pass for all faces of a frame batch
-    (element-wise float64 arithmetic in a fixed association order, so a face's matrix does not depend on its batch)."""
+    (element-wise float64 arithmetic in a fixed association order, so a face's matrix does not depend on its batch).
+    `side`: the side of the square crop; the 112 x 112 template is scaled by side / 112 (112: the embedder's, as it is)."""
     p = np.asarray(landmarks).astype(np.float32).astype(np.float64).reshape(-1, 5, 2)
     q = _TEMPLATE.astype(np.float64)
+    if side != 112:
+        q = q * (side / 112.0)
     px, py = p[:, :, 0], p[:, :, 1]
     pmx = (((px[:, 0] + px[:, 1]) + px[:, 2]) + px[:, 3] + px[:, 4]) / 5.0
     pmy = (((py[:, 0] + py[:, 1]) + py[:, 2]) + py[:, 3] + py[:, 4]) / 5.0

@@ -25,6 +25,10 @@ exif, ...) are not offered.
 `resize_frames(frames, size, resample, box)` resizes resident batches on the GPU (`ta_frames_resample`) with the pixels of
 Pillow's `Image.resize(size, resample, box=box)` bit for bit, for every Pillow filter, and always returns ONE batch, so a
 mixed-size list from `open_images` becomes a batch of a common size (for `encode_jpeg`, a video writer, a network).
+
+`transform_frames`, `transpose_frames` and `rotate_frames` are Pillow's `Image.transform` (AFFINE, PERSPECTIVE),
+`Image.transpose` and `Image.rotate` on resident batches (`ta_frames_transform`, `ta_frames_transpose`), bit for bit:
+sideways video turned upright, a tilted camera de-rotated, a screen or a sign perspective-corrected, without a download.
 """
 import os
 from pathlib import Path
@@ -224,10 +228,15 @@ def resize_frames(frames, size, resample='bicubic', box=None, ctx=None):
         regions['frame'] = np.arange(n)
         regions['x0'], regions['y0'], regions['x1'], regions['y1'] = box if box is not None else (0, 0, w, h)
         parts.append(b.resample(regions, height, width, code, ctx=ctx))
+    return _one_batch(ctx, parts, height, width)
+
+
+def _one_batch(ctx, parts, height, width):
+    """Batches of one size -> one batch with their images in order (the parts are freed); a single part is returned as it is."""
     if len(parts) == 1:
         return parts[0]
     try:
-        out = lib.Frames.zeros(ctx, total, height, width)
+        out = lib.Frames.zeros(ctx, sum(p.shape[0] for p in parts), height, width)
         at = 0
         for p in parts:
             for k in range(p.shape[0]):
@@ -237,6 +246,176 @@ def resize_frames(frames, size, resample='bicubic', box=None, ctx=None):
     finally:
         _free(parts)
     return out
+
+
+def _batches(frames, who):
+    if isinstance(frames, lib.Frames):
+        return [frames], False
+    if isinstance(frames, (list, tuple)) and frames and all(isinstance(b, lib.Frames) for b in frames):
+        return list(frames), True
+    raise ValueError('%s: a lib.Frames batch or a non-empty list of them' % who)
+
+
+def _size(size, who):
+    try:
+        width, height = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('%s: size must be (width, height), got %r' % (who, size)) from None
+    if not (1 <= width <= lib.RESAMPLE_SIDE_LIMIT and 1 <= height <= lib.RESAMPLE_SIDE_LIMIT):
+        raise ValueError('%s: size must be within 1 .. %d a side, got %r' % (who, lib.RESAMPLE_SIDE_LIMIT, size))
+    return width, height
+
+
+def _transform_filter(resample, who):
+    code = lib.resample_filter(resample)
+    if code not in lib.TRANSFORM_FILTERS:
+        raise ValueError("%s: resample must be 'nearest', 'bilinear' or 'bicubic' (Pillow offers no other here), got %r" % (who, resample))
+    return code
+
+
+def _fillcolor(fillcolor, who):
+    if fillcolor is None:
+        return None
+    try:
+        rgb = [int(v) for v in fillcolor]
+    except (TypeError, ValueError):
+        rgb = []
+    if len(rgb) != 3 or not all(0 <= v <= 255 for v in rgb):
+        raise ValueError('%s: fillcolor must be None or three values 0 .. 255, got %r' % (who, fillcolor))
+    return tuple(rgb)
+
+
+def transform_frames(frames, size, method, data, resample='nearest', fillcolor=None, ctx=None):
+    """Resident frames warped -> one NEW resident `lib.Frames` (sum(n), height, width, 3), images in input order, each
+    Pillow's `Image.fromarray(frame).transform(size, method, data, resample=resample, fillcolor=fillcolor)` bit for bit
+    (`ta_frames_transform`).  `frames`: a `lib.Frames` batch or a list of them (as `open_images` returns for mixed sizes);
+    `size`: (width, height); `method`: 'affine' / 'perspective' or Pillow's Image.AFFINE / Image.PERSPECTIVE; `data`:
+    Pillow's 6 (affine) or 8 (perspective) coefficients, OUTPUT to INPUT coordinates, one tuple for all frames or one per
+    frame; `resample`: 'nearest', 'bilinear', 'bicubic' or Pillow's code; `fillcolor`: None (zeros) or (r, g, b).  `ctx`: the
+    context the work runs on and the result belongs to (default: the first batch's own).  Every argument is checked before
+    anything is launched."""
+    who = 'transform_frames'
+    batches, _ = _batches(frames, who)
+    width, height = _size(size, who)
+    code = _transform_filter(resample, who)
+    fill = _fillcolor(fillcolor, who)
+    if isinstance(method, str) and method.lower() in lib.TRANSFORM_METHODS:
+        method = lib.TRANSFORM_METHODS[method.lower()]
+    if isinstance(method, bool) or not isinstance(method, (int, np.integer)) or int(method) not in (lib.AFFINE, lib.PERSPECTIVE):
+        raise ValueError("%s: method must be 'affine' (0) or 'perspective' (2), got %r" % (who, method))
+    method = int(method)
+    count = 6 if method == lib.AFFINE else 8
+    total = sum(b.shape[0] for b in batches)
+    if total == 0:
+        raise ValueError('%s: no images' % who)
+    try:
+        coef = np.asarray(data, np.float64)
+    except (TypeError, ValueError):
+        coef = np.zeros(0)
+    if coef.ndim == 1 and coef.shape[0] == count:
+        coef = np.broadcast_to(coef, (total, count))
+    elif coef.shape != (total, count):
+        raise ValueError('%s: data must be %d coefficients, or %d of them for each of the %d frames' % (who, count, count, total))
+    if not np.isfinite(coef).all():
+        raise ValueError('%s: data must be finite' % who)
+    ctx = ctx if ctx is not None else batches[0].ctx
+    parts, at = [], 0
+    for b in batches:
+        n = b.shape[0]
+        if not n:
+            continue
+        regions = np.zeros(n, lib.TRANSFORM_DT)
+        regions['frame'], regions['method'] = np.arange(n), method
+        regions['a'][:, :count] = coef[at:at + n]
+        at += n
+        parts.append(b.transform(regions, height, width, code, fill, ctx=ctx))
+    return _one_batch(ctx, parts, height, width)
+
+
+def transpose_frames(frames, op, ctx=None):
+    """Pillow's `Image.transpose(op)` of every resident frame (`ta_frames_transpose`): a NEW batch for a batch, a list of new
+    batches, one per input batch, for a list (the sizes of a mixed list stay mixed).  `op`: Pillow's code 0 .. 6 or
+    'flip_left_right', 'flip_top_bottom', 'rotate_90' (counter-clockwise, as in Pillow), 'rotate_180', 'rotate_270',
+    'transpose', 'transverse'."""
+    batches, listed = _batches(frames, 'transpose_frames')
+    code = lib.transpose_op(op)
+    outs = [b.transpose(code, ctx=ctx if ctx is not None else batches[0].ctx) for b in batches]
+    return outs if listed else outs[0]
+
+
+def rotate_plan(width, height, angle, expand=False, center=None, translate=None):
+    """What Pillow's `Image.rotate(angle, resample, expand, center, translate)` does to a width x height image, host only:
+    ('copy', None, size), ('transpose', op, size) for its fast paths (a multiple of 360; 180; 90 and 270 when `expand` is
+    set or the image is square; all only without `center` and `translate`), else ('transform', the six AFFINE
+    coefficients, size) built as Pillow builds them: the rotation rounded to 15 decimals, the expanded canvas from the
+    transformed corners."""
+    import math
+    angle = angle % 360.0
+    if not (center or translate):
+        if angle == 0:
+            return 'copy', None, (width, height)
+        if angle == 180:
+            return 'transpose', lib.ROTATE_180, (width, height)
+        if angle in (90, 270) and (expand or width == height):
+            return 'transpose', lib.ROTATE_90 if angle == 90 else lib.ROTATE_270, (height, width)
+    w, h = width, height
+    post_trans = (0, 0) if translate is None else translate
+    if center is None:
+        center = (w / 2, h / 2)
+    angle = -math.radians(angle)
+    matrix = [round(math.cos(angle), 15), round(math.sin(angle), 15), 0.0,
+              round(-math.sin(angle), 15), round(math.cos(angle), 15), 0.0]
+
+    def transform(x, y, matrix):
+        a, b, c, d, e, f = matrix
+        return a * x + b * y + c, d * x + e * y + f
+    matrix[2], matrix[5] = transform(-center[0] - post_trans[0], -center[1] - post_trans[1], matrix)
+    matrix[2] += center[0]
+    matrix[5] += center[1]
+    if expand:
+        xx, yy = zip(*[transform(x, y, matrix) for x, y in ((0, 0), (w, 0), (w, h), (0, h))])
+        nw = math.ceil(max(xx)) - math.floor(min(xx))
+        nh = math.ceil(max(yy)) - math.floor(min(yy))
+        matrix[2], matrix[5] = transform(-(nw - w) / 2.0, -(nh - h) / 2.0, matrix)
+        w, h = nw, nh
+    return 'transform', matrix, (w, h)
+
+
+def rotate_frames(frames, angle, resample='nearest', expand=False, center=None, translate=None, fillcolor=None, ctx=None):
+    """Pillow's `Image.rotate(angle, resample, expand, center, translate, fillcolor)` of every resident frame, bit for bit:
+    a NEW batch for a batch, a list of new batches for a list.  It takes the paths Pillow takes (`rotate_plan`): a copy, a
+    `ta_frames_transpose`, or one `ta_frames_transform` call per batch with Pillow's matrix.  `angle`: degrees
+    counter-clockwise; `center`, `translate`: (x, y) or None."""
+    who = 'rotate_frames'
+    batches, listed = _batches(frames, who)
+    code = _transform_filter(resample, who)
+    fill = _fillcolor(fillcolor, who)
+    try:
+        angle = float(angle)
+        center = None if center is None else tuple(float(v) for v in center)
+        translate = None if translate is None else tuple(float(v) for v in translate)
+    except (TypeError, ValueError):
+        raise ValueError('%s: angle must be a number, center and translate None or (x, y)' % who) from None
+    if not np.isfinite(angle) or any(t is not None and (len(t) != 2 or not np.isfinite(t).all()) for t in (center, translate)):
+        raise ValueError('%s: angle must be finite, center and translate None or two finite values' % who)
+    if any(b.shape[0] == 0 for b in batches):
+        raise ValueError('%s: a batch without images' % who)
+    plans = [rotate_plan(b.shape[2], b.shape[1], angle, expand, center, translate) for b in batches]
+    for kind, _, size in plans:
+        _size(size, who)
+    outs = []
+    for b, (kind, arg, (width, height)) in zip(batches, plans):
+        on = ctx if ctx is not None else batches[0].ctx
+        n = b.shape[0]
+        if kind == 'transpose':
+            outs.append(b.transpose(arg, ctx=on))
+            continue
+        regions = np.zeros(n, lib.TRANSFORM_DT)
+        regions['frame'], regions['method'] = np.arange(n), lib.AFFINE
+        regions['a'][:, :6] = (1, 0, 0, 0, 1, 0) if kind == 'copy' else arg
+        out = b.transform(regions, height, width, lib.NEAREST if kind == 'copy' else code, fill, ctx=on)
+        outs.append(out)
+    return outs if listed else outs[0]
 
 
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}

@@ -57,6 +57,8 @@ SIGNATURES = {
     'ta_frames_resample': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, P(c_void_p)]),
     'ta_resample_plan': (c_int, [c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_int, P(c_int)]),
     'ta_frames_pixelate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'ta_frames_transform': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, P(c_void_p)]),
+    'ta_frames_transpose': (c_int, [c_void_p, c_void_p, c_int, P(c_void_p)]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -162,6 +164,26 @@ def resample_plan(in_size, b0, b1, out_size, filter):
     if rc != OK:
         raise TerranAmdError(rc, 'resample_plan(%r, %r, %r, %r, %r)' % (in_size, b0, b1, out_size, filter))
     return bounds, coefs
+
+
+# ta_transform_region (include/terran_amd.h), the methods TA_TRANSFORM_* and the ops of ta_frames_transpose: Pillow's codes
+AFFINE, PERSPECTIVE = 0, 2
+TRANSFORM_METHODS = {'affine': AFFINE, 'perspective': PERSPECTIVE}
+TRANSFORM_FILTERS = (NEAREST, BILINEAR, BICUBIC)
+TRANSFORM_DT = np.dtype([('frame', '<i4'), ('method', '<i4'), ('a', '<f8', (8,))])
+assert TRANSFORM_DT.itemsize == 72
+FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM, ROTATE_90, ROTATE_180, ROTATE_270, TRANSPOSE, TRANSVERSE = range(7)
+TRANSPOSE_OPS = {'flip_left_right': FLIP_LEFT_RIGHT, 'flip_top_bottom': FLIP_TOP_BOTTOM, 'rotate_90': ROTATE_90,
+                 'rotate_180': ROTATE_180, 'rotate_270': ROTATE_270, 'transpose': TRANSPOSE, 'transverse': TRANSVERSE}
+
+
+def transpose_op(op):
+    """An op's name ('flip_left_right', ..., 'transverse') or Pillow's integer code -> the code, or ValueError."""
+    if isinstance(op, str) and op.lower() in TRANSPOSE_OPS:
+        return TRANSPOSE_OPS[op.lower()]
+    if isinstance(op, (int, np.integer)) and not isinstance(op, bool) and 0 <= int(op) <= 6:
+        return int(op)
+    raise ValueError('op must be one of %s or Pillow\'s code 0 .. 6, got %r' % (sorted(TRANSPOSE_OPS), op))
 
 
 # ta_jpeg_header and the decode paths TA_JPEG_* (include/terran_amd.h)
@@ -586,6 +608,27 @@ class Frames:
         ctx = ctx or self.ctx
         regions = np.ascontiguousarray(regions, dtype=PIXELATE_DT)
         ctx.check(ctx.lib.ta_frames_pixelate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+
+    def transform(self, regions, out_h, out_w, filter, fill=None, ctx=None):
+        """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), method, a,
+        resample=filter, fillcolor=fill) of the frame regions[i] names (a TRANSFORM_DT array; ta_frames_transform), or None
+        without regions.  `filter`: NEAREST, BILINEAR or BICUBIC; `fill`: None (zeros) or 3 values 0 .. 255.  `ctx`: the
+        context the work runs on and the result belongs to -- the CALLER's, as in `resize`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=TRANSFORM_DT)
+        rgb = None if fill is None else np.array(fill, np.uint8).reshape(3)
+        hd = c_void_p()
+        ctx.check(ctx.lib.ta_frames_transform(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), int(out_h),
+                                              int(out_w), int(filter), ptr(rgb), C.byref(hd)))
+        return Frames(ctx, handle=hd) if hd.value else None
+
+    def transpose(self, op, ctx=None):
+        """A NEW batch: Pillow's Image.transpose(op) of every image (ta_frames_transpose).  `op`: FLIP_LEFT_RIGHT ..
+        TRANSVERSE, Pillow's codes.  `ctx`: the caller's, as in `resize`."""
+        ctx = ctx or self.ctx
+        hd = c_void_p()
+        ctx.check(ctx.lib.ta_frames_transpose(ctx.h, self.h, int(op), C.byref(hd)))
+        return Frames(ctx, handle=hd)
 
     def encode_jpeg(self, quality=75, subsampling=2, ctx=None, optimize=False):
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs

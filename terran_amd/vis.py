@@ -28,7 +28,9 @@ csrc/resample.hip).  `crop_faces` cuts the same boxes out of a resident batch as
 take as it is.
 
 Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch, the
-blurring one ta_frames_blur or ta_frames_pixelate call, the cropping one ta_frames_resample call.  Importing this module needs no GPU and no Pillow.
+blurring one ta_frames_blur or ta_frames_pixelate call, the cropping one ta_frames_resample call, the aligned chips of
+`align_faces` (the embedder's five-point similarity, Pillow's Image.transform; csrc/transform.hip) one ta_frames_transform
+call.  Importing this module needs no GPU and no Pillow.
 """
 import collections
 import math
@@ -446,6 +448,46 @@ def crop_faces(frames, faces_per_frame, size=(112, 112), margin=0.0, resample='b
     if not len(regions):
         return None, index
     return frames.resample(regions, height, width, code, ctx=ctx), index
+
+
+def pack_align(faces_per_frame, side=112):
+    """-> (lib.TRANSFORM_DT array, int32 (n, 2) index of (frame, face) pairs): for every face, in order, frame by frame, the
+    AFFINE map of its landmark-aligned side x side chip -- the five-point similarity the embedder cuts its crops with
+    (arcface.align_matrices; the template scaled by side / 112).  A face without 'landmarks' raises ValueError.  Host only."""
+    from . import arcface
+    lms, index = [], []
+    for f, faces in enumerate(faces_per_frame):
+        for k, face in enumerate(_as_list(faces)):
+            lm = face.get('landmarks') if hasattr(face, 'get') else None
+            if lm is None or np.asarray(lm).shape != (5, 2) or not np.isfinite(np.asarray(lm, np.float64)).all():
+                raise ValueError('align_faces: face %d of frame %d has no (5, 2) finite landmarks' % (k, f))
+            lms.append(np.asarray(lm))
+            index.append((f, k))
+    regions = np.zeros(len(lms), lib.TRANSFORM_DT)
+    if lms:
+        regions['frame'] = [f for f, _ in index]
+        regions['method'] = lib.AFFINE
+        regions['a'][:, :6] = arcface.align_matrices(np.stack(lms), side)
+    return regions, np.array(index, np.int32).reshape(-1, 2)
+
+
+def align_faces(frames, faces_per_frame, size=(112, 112), resample='bilinear', ctx=None):
+    """Cut the landmark-aligned chips of the faces of the resident batch `frames` (lib.Frames) -> (chips, index) as
+    `crop_faces` returns them: `chips` one resident (n_faces, side, side, 3) RGB lib.Frames (None when there is no face),
+    each Pillow's `Image.fromarray(frame).transform(size, AFFINE, matrix, resample)` with the embedder's five-point
+    similarity (at (112, 112) bilinear: the very crops the embedder sees, bit for bit); `index` the int32 (n_faces, 2)
+    (frame, face) pairs.  `size`: (side, side), square; `resample`: 'nearest', 'bilinear', 'bicubic' or Pillow's code."""
+    _check_batch(frames, faces_per_frame)
+    width, height = _chip_size(size)
+    if width != height:
+        raise ValueError('align_faces: size must be square (the template is), got %r' % (size,))
+    code = lib.resample_filter(resample)
+    if code not in lib.TRANSFORM_FILTERS:
+        raise ValueError("align_faces: resample must be 'nearest', 'bilinear' or 'bicubic', got %r" % (resample,))
+    regions, index = pack_align(faces_per_frame, width)
+    if not len(regions):
+        return None, []
+    return frames.transform(regions, height, width, code, ctx=ctx), index
 
 
 def _chip_size(size):
