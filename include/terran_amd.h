@@ -255,6 +255,56 @@ int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_transform_re
 #define TA_TRANSVERSE 6
 int ta_frames_transpose(ta_ctx* ctx, const ta_frames* src, int op, ta_frames** out);
 
+/* ---- pixel values: histograms, look-up tables, saturation ---------------------------------- */
+/* Regions of the three calls below are as ta_frames_blur takes them: a half-open box [x0, x1) x [y0, y1) inside the
+ * frame, no side longer than 16384, TA_BLUR_BOX or TA_BLUR_ELLIPSE (only the pixels of
+ * ImageDraw.ellipse([0, 0, w - 1, h - 1], fill=) in the box count or change; a 1 x 1 box has none).  Every call runs on
+ * `ctx`'s stream (a batch of another context on the same device may be passed) and returns when it is done.  n = 0:
+ * TA_OK.  TA_E_INVALID, before any launch, any changed pixel and any written output: a frame index out of range; a box
+ * that is empty, inverted, not inside the frame or has a side longer than 16384; an unknown shape; and what each call adds.
+ *
+ * Histogram of every region, Pillow's
+ *     TA_HIST_RGB  im.crop(box).histogram(mask)                768 counts: R bins, G bins, B bins
+ *     TA_HIST_L    im.crop(box).convert('L').histogram(mask)   256 counts of (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ * into the HOST array hist[n][768 or 256] (mask: the shape's coverage).  Regions only read: they may overlap, repeat and
+ * name the frames in any order; a clear and one launch serve them all.  Counts are integers, so the result does not
+ * depend on the order of accumulation.  TA_E_INVALID also: an unknown mode, hist = NULL. */
+#define TA_HIST_RGB 0
+#define TA_HIST_L 1
+typedef struct ta_hist_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+} ta_hist_region;
+int ta_frames_histogram(ta_ctx* ctx, const ta_frames* frames, const ta_hist_region* regions, int n, int mode, uint32_t* hist);
+
+/* Applies look-up tables to regions of `frames` in place, Pillow's
+ *     im.paste(im.crop(box).point(lut), box)             under the ellipse shape only the ellipse's pixels change
+ * `luts`: a HOST array of n_luts tables of 768 bytes, Pillow's point() argument for RGB (R table, G table, B table);
+ * region i uses table regions[i].lut.  Regions of one frame apply in list order where they overlap (rounds of pairwise
+ * disjoint regions, one launch per round).  TA_E_INVALID also: a `lut` outside 0 .. n_luts - 1, luts = NULL. */
+typedef struct ta_point_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  int32_t lut;           /* index into `luts`                         */
+} ta_point_region;
+int ta_frames_point(ta_ctx* ctx, ta_frames* frames, const ta_point_region* regions, int n, const uint8_t* luts, int n_luts);
+
+/* Blends every pixel of the regions with its own luma in place, Pillow's
+ *     im.paste(ImageEnhance.Color(im.crop(box)).enhance(factor), box)
+ * bit for bit: L = (19595 R + 38470 G + 7471 B + 0x8000) >> 16, then per band Image.blend's float32 expression
+ * L + factor * (v - L), a multiply and an add, never fused: truncated when 0 <= factor <= 1, clipped to 0 .. 255 first
+ * otherwise; factor 0 is convert('L').convert('RGB'), factor 1 leaves the region as it is.  Order and rounds are
+ * ta_frames_point's.  TA_E_INVALID also: a factor that is NaN or infinite. */
+typedef struct ta_saturate_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  float factor;          /* ImageEnhance.Color's                      */
+} ta_saturate_region;
+int ta_frames_saturate(ta_ctx* ctx, ta_frames* frames, const ta_saturate_region* regions, int n);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

@@ -29,6 +29,13 @@ mixed-size list from `open_images` becomes a batch of a common size (for `encode
 `transform_frames`, `transpose_frames` and `rotate_frames` are Pillow's `Image.transform` (AFFINE, PERSPECTIVE),
 `Image.transpose` and `Image.rotate` on resident batches (`ta_frames_transform`, `ta_frames_transpose`), bit for bit:
 sideways video turned upright, a tilted camera de-rotated, a screen or a sign perspective-corrected, without a download.
+
+Pixel values: `histogram_frames` / `frame_stats` are Pillow's `Image.histogram` and `ImageStat.Stat` of resident frames
+(`ta_frames_histogram`; only the counts leave the device), and `point_frames`, `equalize_frames`, `autocontrast_frames`,
+`brightness_frames`, `contrast_frames`, `color_frames`, `grayscale_frames`, `invert_frames`, `posterize_frames` and
+`solarize_frames` change resident frames in place with the pixels of `Image.point`, `ImageOps` and `ImageEnhance`, bit
+for bit (`ta_frames_point`, `ta_frames_saturate`): at most one histogram call, tables built on the host by the `*_lut`
+functions (usable without a device), and one in-place call per batch.
 """
 import os
 from pathlib import Path
@@ -416,6 +423,319 @@ def rotate_frames(frames, angle, resample='nearest', expand=False, center=None, 
         out = b.transform(regions, height, width, lib.NEAREST if kind == 'copy' else code, fill, ctx=on)
         outs.append(out)
     return outs if listed else outs[0]
+
+
+# ---- pixel values: histograms, statistics, look-up tables ---------------------------------------------------------------
+def _frame_boxes(batches, boxes, who):
+    """-> per batch an int (n, 4) array of half-open boxes (x0, y0, x1, y1), one per frame: `boxes` (one per frame of the
+    whole input, in order) or the whole frames; checked against the frames here, before anything is launched."""
+    total = sum(b.shape[0] for b in batches)
+    if total == 0:
+        raise ValueError('%s: no images' % who)
+    if boxes is not None:
+        try:
+            boxes = np.asarray(boxes)
+            ok = boxes.shape == (total, 4) and np.array_equal(boxes, boxes.astype(np.int64))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError('%s: boxes must be one integer (x0, y0, x1, y1) for each of the %d frames' % (who, total))
+        boxes = boxes.astype(np.int64)
+    out, at = [], 0
+    for b in batches:
+        n, h, w = b.shape[:3]
+        q = boxes[at:at + n] if boxes is not None else np.tile(np.array([0, 0, w, h], np.int64), (n, 1))
+        at += n
+        if len(q) and not ((0 <= q[:, 0]) & (q[:, 0] < q[:, 2]) & (q[:, 2] <= w) & (0 <= q[:, 1]) & (q[:, 1] < q[:, 3]) & (q[:, 3] <= h)).all():
+            raise ValueError('%s: every box must satisfy 0 <= x0 < x1 <= %d and 0 <= y0 < y1 <= %d' % (who, w, h))
+        out.append(q)
+    return out
+
+
+def _regions(dt, boxes, shape=lib.BLUR_BOX):
+    q = np.zeros(len(boxes), dt)
+    q['frame'] = np.arange(len(boxes))
+    q['x0'], q['y0'], q['x1'], q['y1'] = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    q['shape'] = shape
+    return q
+
+
+def _hist_mode(mode, who):
+    if mode not in lib.HIST_MODES:
+        raise ValueError("%s: mode must be 'RGB' or 'L', got %r" % (who, mode))
+    return lib.HIST_MODES[mode]
+
+
+def histogram_frames(frames, mode='RGB', boxes=None, ctx=None):
+    """Pillow's `Image.histogram()` of every resident frame -> uint32 (N, 3, 256) (mode 'RGB': the R, G and B counts), or
+    (N, 256) for mode 'L': the histogram of `convert('L')`.  `frames`: a `lib.Frames` batch or a list of them (N frames in
+    all, in order); `boxes`: None, or one half-open integer (x0, y0, x1, y1) per frame: the histogram of `crop(box)`.  One
+    `ta_frames_histogram` call per batch; only the counts leave the device."""
+    who = 'histogram_frames'
+    batches, _ = _batches(frames, who)
+    code = _hist_mode(mode, who)
+    per_batch = _frame_boxes(batches, boxes, who)
+    parts = [b.histogram(_regions(lib.HIST_DT, q), code, ctx=ctx) for b, q in zip(batches, per_batch) if len(q)]
+    return np.concatenate(parts)
+
+
+def histogram_stats(hist):
+    """`ImageStat.Stat(histogram)` for a stack of histograms, host only: `hist` integer (..., 256), one row of counts per
+    band -> dict of arrays shaped like hist[..., 0]: `count` (int64), `sum`, `sum2`, `mean`, `rms`, `var`, `stddev`
+    (float64), `median` (int64), and `extrema` (int64, one more axis: min, max).  Every value is what Stat computes, in its
+    order of float64 operations: the sums are integers below 2^53, so they are exact in any order; the quotients, the
+    `** 2.0` and the roots are Python's.  A band without pixels gives Stat's values: mean, rms and var 0, median 255,
+    extrema (255, 0)."""
+    import math
+    h = np.asarray(hist)
+    if h.ndim < 1 or h.shape[-1] != 256 or h.dtype.kind not in 'iu':
+        raise ValueError('histogram_stats: integer counts (..., 256), got %s %s' % (h.dtype, h.shape))
+    shape = h.shape[:-1]
+    h = h.reshape(-1, 256).astype(np.int64)
+    j = np.arange(256, dtype=np.int64)
+    count, total, total2 = h.sum(1), (h * j).sum(1), (h * (j * j)).sum(1)
+    m = len(h)
+    out = {k: np.zeros(m, np.float64) for k in ('sum', 'sum2', 'mean', 'rms', 'var', 'stddev')}
+    median, extrema = np.full(m, 255, np.int64), np.tile(np.array([255, 0], np.int64), (m, 1))
+    for i in range(m):
+        n, s, s2 = int(count[i]), float(int(total[i])), float(int(total2[i]))
+        out['sum'][i], out['sum2'][i] = s, s2
+        if n:
+            out['mean'][i] = s / n
+            out['rms'][i] = math.sqrt(s2 / n)
+            out['var'][i] = (s2 - (s ** 2.0) / n) / n
+            used = np.nonzero(h[i])[0]
+            extrema[i] = used[0], used[-1]
+            median[i] = min(int(np.searchsorted(np.cumsum(h[i]), n // 2, side='right')), 255)
+        out['stddev'][i] = math.sqrt(out['var'][i])
+    out = {k: v.reshape(shape) for k, v in out.items()}
+    out.update(count=count.reshape(shape), median=median.reshape(shape), extrema=extrema.reshape(shape + (2,)))
+    return out
+
+
+def frame_stats(frames, mode='RGB', boxes=None, ctx=None):
+    """`ImageStat.Stat` of every resident frame (or of `crop(box)` of each: `boxes` as in `histogram_frames`) -> dict of
+    arrays (N, 3) for mode 'RGB', (N, 1) for mode 'L' (Stat of `convert('L')`): `histogram_stats` of one
+    `histogram_frames` call, equal to Stat's values exactly."""
+    hist = histogram_frames(frames, mode, boxes, ctx=ctx)
+    return histogram_stats(hist if hist.ndim == 3 else hist[:, None])
+
+
+def _bands(hist, who):
+    h = np.asarray(hist)
+    if h.size == 0 or h.size % 256 or h.dtype.kind not in 'iu':
+        raise ValueError('%s: integer counts, 256 per band, got %s %s' % (who, h.dtype, h.shape))
+    return [[int(v) for v in row] for row in h.reshape(-1, 256)]
+
+
+def equalize_lut(hist):
+    """The table `ImageOps.equalize` applies to an image with this histogram, host only: `hist` 256 counts per band ((256,),
+    (3, 256) or (768,)) -> uint8 (256 x bands,).  Pillow's integer steps: the non-zero counts without the last one, summed
+    and floor-divided by 255, give the step (a band with one used bin, or a step of 0: the identity); entry i is
+    (step // 2 + counts below i) // step, clipped to 255 as point() clips it."""
+    lut = []
+    for h in _bands(hist, 'equalize_lut'):
+        histo = [v for v in h if v]
+        step = (sum(histo) - histo[-1]) // 255 if len(histo) > 1 else 0
+        if not step:
+            lut.extend(range(256))
+            continue
+        n = step // 2
+        for i in range(256):
+            lut.append(min(n // step, 255))             # point() clips its table's entries; the quotient can pass 255
+            n += h[i]
+    return np.array(lut, np.uint8)
+
+
+def autocontrast_lut(hist, cutoff=0, ignore=None):
+    """The table `ImageOps.autocontrast(cutoff=, ignore=)` applies to an image with this histogram, host only; `hist` and
+    the result as in `equalize_lut`.  `cutoff`: percent cut from both ends, or (low, high); `ignore`: a bin or bins whose
+    counts are dropped first.  Pillow's steps: int(n * cutoff // 100) counts removed from each end, the lowest and highest
+    bin left, the identity when hi <= lo, else int(i * (255.0 / (hi - lo)) - lo * scale) clipped to 0 .. 255."""
+    if cutoff and not isinstance(cutoff, tuple):
+        cutoff = (cutoff, cutoff)
+    ignore = [] if ignore is None else ([int(ignore)] if isinstance(ignore, (int, np.integer)) else [int(v) for v in ignore])
+    lut = []
+    for h in _bands(hist, 'autocontrast_lut'):
+        for ix in ignore:
+            h[ix] = 0
+        if cutoff:
+            n = sum(h)
+            for c, order in ((cutoff[0], range(256)), (cutoff[1], range(255, -1, -1))):
+                cut = int(n * c // 100)
+                for i in order:
+                    if cut > h[i]:
+                        cut -= h[i]
+                        h[i] = 0
+                    else:
+                        h[i] -= cut
+                        cut = 0
+                    if cut <= 0:
+                        break
+        used = [i for i in range(256) if h[i]]
+        lo, hi = (used[0], used[-1]) if used else (255, 0)
+        if hi <= lo:
+            lut.extend(range(256))
+            continue
+        scale = 255.0 / (hi - lo)
+        offset = -lo * scale
+        lut.extend(min(max(int(ix * scale + offset), 0), 255) for ix in range(256))
+    return np.array(lut, np.uint8)
+
+
+def _factor(factor, who):
+    try:
+        f = np.float32(factor)                          # Image.blend takes its alpha as a C float
+    except (TypeError, ValueError):
+        f = np.float32(np.nan)
+    if not np.isfinite(f):
+        raise ValueError('%s: factor must be a finite number, got %r' % (who, factor))
+    return f
+
+
+def blend_lut(in1, factor):
+    """`Image.blend(Image.new('L', size, in1), im, factor)` as a table over im's values, host only -> uint8 (256,):
+    libImaging's float32 in1 + factor * (v - in1), a multiply and an add; truncated when 0 <= factor <= 1, clipped to
+    0 .. 255 first otherwise; factor 0 copies in1, factor 1 the image."""
+    f = _factor(factor, 'blend_lut')
+    in1 = int(in1)
+    if not 0 <= in1 <= 255:
+        raise ValueError('blend_lut: in1 must be within 0 .. 255, got %r' % (in1,))
+    v = np.arange(256, dtype=np.int32)
+    if f == 0:
+        return np.full(256, in1, np.uint8)
+    if f == 1:
+        return v.astype(np.uint8)
+    t = np.float32(in1) + f * (v - in1).astype(np.float32)
+    assert t.dtype == np.float32
+    if 0 <= f <= 1:
+        return t.astype(np.int32).astype(np.uint8)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, np.clip(t, 0, 255).astype(np.int32))).astype(np.uint8)
+
+
+def brightness_lut(factor):
+    """The table of `ImageEnhance.Brightness(im).enhance(factor)`: a blend with black."""
+    return blend_lut(0, _factor(factor, 'brightness_lut'))
+
+
+def contrast_lut(factor, mean):
+    """The table of `ImageEnhance.Contrast(im).enhance(factor)` for an image whose `convert('L')` has the mean `mean`
+    (`ImageStat`'s float, as `frame_stats(frames, 'L')['mean']` returns it): a blend with the grey int(mean + 0.5)."""
+    return blend_lut(int(float(mean) + 0.5), _factor(factor, 'contrast_lut'))
+
+
+def invert_lut():
+    """The table of `ImageOps.invert`."""
+    return np.arange(255, -1, -1).astype(np.uint8)
+
+
+def posterize_lut(bits):
+    """The table of `ImageOps.posterize(im, bits)`: the top `bits` bits (1 .. 8) of every value."""
+    if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 1 <= bits <= 8:
+        raise ValueError('posterize_lut: bits must be an int within 1 .. 8, got %r' % (bits,))
+    return (np.arange(256) & ~(2 ** (8 - int(bits)) - 1)).astype(np.uint8)
+
+
+def solarize_lut(threshold=128):
+    """The table of `ImageOps.solarize(im, threshold)`: values from `threshold` on are inverted."""
+    i = np.arange(256)
+    return np.where(i < threshold, i, 255 - i).astype(np.uint8)
+
+
+def _tables(lut, total, who):
+    """-> uint8 (1, 768) or (total, 768): a table of 256 entries (all bands), 768 (R, G, B), or one of 768 per frame."""
+    try:
+        a = np.asarray(lut)
+        ok = a.dtype.kind in 'iu' and a.size and int(a.min()) >= 0 and int(a.max()) <= 255
+    except (TypeError, ValueError):
+        ok = False
+    if ok and a.shape == (256,):
+        return np.tile(a.astype(np.uint8), 3)[None]
+    if ok and a.shape == (768,):
+        return a.astype(np.uint8)[None]
+    if ok and a.shape == (total, 768):
+        return np.ascontiguousarray(a.astype(np.uint8))
+    raise ValueError('%s: a table of 256 or 768 integers within 0 .. 255, or one of 768 for each of the %d frames' % (who, total))
+
+
+def point_frames(frames, lut, ctx=None):
+    """Pillow's `Image.point(lut)` of every resident frame, in place (`ta_frames_point`, one call per batch); returns
+    `frames`.  `frames`: a `lib.Frames` batch or a list of them; `lut`: 256 entries (applied to the three bands), 768 (R, G
+    and B table), or (N, 768): a table per frame."""
+    who = 'point_frames'
+    batches, _ = _batches(frames, who)
+    per_batch = _frame_boxes(batches, None, who)
+    tables = _tables(lut, sum(len(q) for q in per_batch), who)
+    at = 0
+    for b, q in zip(batches, per_batch):
+        regions = _regions(lib.POINT_DT, q)
+        if len(tables) > 1:
+            regions['lut'] = np.arange(len(q))
+        if len(q):
+            b.point(regions, tables[at:at + len(q)] if len(tables) > 1 else tables, ctx=ctx)
+        at += len(q)
+    return frames
+
+
+def equalize_frames(frames, ctx=None):
+    """`ImageOps.equalize` of every resident frame, in place: one histogram call, a table per frame, one point call."""
+    hist = histogram_frames(frames, 'RGB', ctx=ctx)
+    return point_frames(frames, np.stack([equalize_lut(h) for h in hist]), ctx=ctx)
+
+
+def autocontrast_frames(frames, cutoff=0, ignore=None, preserve_tone=False, ctx=None):
+    """`ImageOps.autocontrast(im, cutoff, ignore, preserve_tone=)` of every resident frame, in place.  `preserve_tone`: one
+    table from the histogram of `convert('L')` for the three bands, instead of a table per band."""
+    hist = histogram_frames(frames, 'L' if preserve_tone else 'RGB', ctx=ctx)
+    luts = [autocontrast_lut(h, cutoff, ignore) for h in hist]
+    return point_frames(frames, np.stack([np.tile(t, 3) if preserve_tone else t for t in luts]), ctx=ctx)
+
+
+def brightness_frames(frames, factor, ctx=None):
+    """`ImageEnhance.Brightness(im).enhance(factor)` of every resident frame, in place."""
+    return point_frames(frames, brightness_lut(factor), ctx=ctx)
+
+
+def contrast_frames(frames, factor, ctx=None):
+    """`ImageEnhance.Contrast(im).enhance(factor)` of every resident frame, in place: each frame blended with the grey of
+    its own mean luma, which comes from one 'L' histogram call."""
+    f = _factor(factor, 'contrast_frames')
+    mean = frame_stats(frames, 'L', ctx=ctx)['mean'][:, 0]
+    return point_frames(frames, np.stack([np.tile(contrast_lut(f, m), 3) for m in mean]), ctx=ctx)
+
+
+def color_frames(frames, factor, ctx=None):
+    """`ImageEnhance.Color(im).enhance(factor)` of every resident frame, in place (`ta_frames_saturate`): every pixel blended
+    with its own luma; 0 greys the frame, values above 1 saturate it."""
+    who = 'color_frames'
+    f = _factor(factor, who)
+    batches, _ = _batches(frames, who)
+    for b, q in zip(batches, _frame_boxes(batches, None, who)):
+        regions = _regions(lib.SATURATE_DT, q)
+        regions['factor'] = f
+        if len(q):
+            b.saturate(regions, ctx=ctx)
+    return frames
+
+
+def grayscale_frames(frames, ctx=None):
+    """`im.convert('L').convert('RGB')` of every resident frame, in place."""
+    return color_frames(frames, 0.0, ctx=ctx)
+
+
+def invert_frames(frames, ctx=None):
+    """`ImageOps.invert` of every resident frame, in place."""
+    return point_frames(frames, invert_lut(), ctx=ctx)
+
+
+def posterize_frames(frames, bits, ctx=None):
+    """`ImageOps.posterize(im, bits)` of every resident frame, in place."""
+    return point_frames(frames, posterize_lut(bits), ctx=ctx)
+
+
+def solarize_frames(frames, threshold=128, ctx=None):
+    """`ImageOps.solarize(im, threshold)` of every resident frame, in place."""
+    return point_frames(frames, solarize_lut(threshold), ctx=ctx)
 
 
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}

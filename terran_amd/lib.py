@@ -59,6 +59,9 @@ SIGNATURES = {
     'ta_frames_pixelate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_frames_transform': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, P(c_void_p)]),
     'ta_frames_transpose': (c_int, [c_void_p, c_void_p, c_int, P(c_void_p)]),
+    'ta_frames_histogram': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    'ta_frames_point': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    'ta_frames_saturate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -138,6 +141,18 @@ PIXELATE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '
                         ('block', '<i4')])
 assert PIXELATE_DT.itemsize == 28
 RESAMPLE_SIDE_LIMIT = 16384                             # an output side, a pixelate block
+
+# ta_hist_region, ta_point_region, ta_saturate_region (include/terran_amd.h) and the modes TA_HIST_*; shapes: BLUR_*
+HIST_RGB, HIST_L = 0, 1
+HIST_MODES = {'RGB': HIST_RGB, 'L': HIST_L}
+HIST_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4')])
+assert HIST_DT.itemsize == 24
+POINT_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                     ('lut', '<i4')])
+assert POINT_DT.itemsize == 28
+SATURATE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                        ('factor', '<f4')])
+assert SATURATE_DT.itemsize == 28
 
 
 def resample_filter(resample):
@@ -608,6 +623,36 @@ class Frames:
         ctx = ctx or self.ctx
         regions = np.ascontiguousarray(regions, dtype=PIXELATE_DT)
         ctx.check(ctx.lib.ta_frames_pixelate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+
+    def histogram(self, regions, mode=HIST_RGB, ctx=None):
+        """uint32 (len(regions), 3, 256) (HIST_RGB) or (len(regions), 256) (HIST_L): Pillow's histogram of each region of a
+        HIST_DT array under its shape (ta_frames_histogram).  The batch is only read.  `ctx`: the CALLER's, as in `blur`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=HIST_DT)
+        mode = int(mode)
+        hist = np.zeros((len(regions), 3, 256) if mode == HIST_RGB else (len(regions), 256), np.uint32)
+        ctx.check(ctx.lib.ta_frames_histogram(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), mode,
+                                              ptr(hist) if len(regions) else None))
+        return hist
+
+    def point(self, regions, luts, ctx=None):
+        """Apply look-up tables to `regions` (a POINT_DT array, in order) of this batch in place (ta_frames_point): Pillow's
+        point() of each half-open box, pasted back under its shape.  `luts`: uint8 (n_luts, 768), R, G and B table of each;
+        a region's `lut` names its table."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=POINT_DT)
+        luts = np.ascontiguousarray(luts, dtype=np.uint8)
+        if luts.ndim != 2 or luts.shape[1] != 768:
+            raise ValueError('point: luts must be uint8 (n_luts, 768), got %s' % (luts.shape,))
+        ctx.check(ctx.lib.ta_frames_point(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions),
+                                          ptr(luts) if len(luts) else None, len(luts)))
+
+    def saturate(self, regions, ctx=None):
+        """Blend `regions` (a SATURATE_DT array, in order) of this batch with their own luma in place (ta_frames_saturate):
+        Pillow's ImageEnhance.Color(region).enhance(factor), pasted back under its shape."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=SATURATE_DT)
+        ctx.check(ctx.lib.ta_frames_saturate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
 
     def transform(self, regions, out_h, out_w, filter, fill=None, ctx=None):
         """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), method, a,

@@ -411,6 +411,38 @@ def pack_crops(faces_per_frame, shapes, margin=0.0):
     return np.array(rows, lib.RESAMPLE_DT), np.array(index, np.int32).reshape(-1, 2)
 
 
+def pack_stats(faces_per_frame, shapes, margin=0.0, shape='box'):
+    """-> (lib.HIST_DT array, int32 (n, 2) index of (frame, face) pairs): pack_blur's regions (the same margin, truncation,
+    clipping and order) for Frames.histogram; a face whose region is empty is left out of both.  Host only."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    rows, index = [], []
+    for f, k, x0, y0, x1, y1 in _clipped_boxes(faces_per_frame, shapes, margin):
+        rows.append((f, x0, y0, x1, y1, BLUR_SHAPES[shape]))
+        index.append((f, k))
+    return np.array(rows, lib.HIST_DT), np.array(index, np.int32).reshape(-1, 2)
+
+
+def face_stats(frames, faces_per_frame, margin=0.0, shape='box', mode='RGB', ctx=None):
+    """Exposure statistics of the faces of the resident batch `frames` (lib.Frames) -> (stats, index): `stats` is
+    `image.histogram_stats` of one `ta_frames_histogram` call over the faces' boxes as pack_blur clips them -- Pillow's
+    `ImageStat.Stat(frame.crop(box))` (mode 'L': of its `convert('L')`), under `shape` 'ellipse' with the ellipse Pillow
+    draws into the box as Stat's mask -- a dict of arrays (n_faces, 3) or (n_faces, 1), plus 'histogram', the uint32 counts
+    they come from; `index` the int32 (n_faces, 2) (frame, face) pairs, as `crop_faces` returns them.  (None, []) when
+    there is no face.  Choosing the best-exposed chip of a track is an argmax over these."""
+    from . import image
+    _check_batch(frames, faces_per_frame)
+    if mode not in lib.HIST_MODES:
+        raise ValueError("mode must be 'RGB' or 'L', got %r" % (mode,))
+    regions, index = pack_stats(faces_per_frame, frames.shape, margin, shape)
+    if not len(regions):
+        return None, []
+    hist = frames.histogram(regions, lib.HIST_MODES[mode], ctx=ctx)
+    stats = image.histogram_stats(hist if hist.ndim == 3 else hist[:, None])
+    stats['histogram'] = hist
+    return stats, index
+
+
 def _clipped_boxes(faces_per_frame, shapes, margin):
     """[(frame, face, x0, y0, x1, y1)]: every face's bbox widened by `margin`, int()-truncated and clipped to its frame,
     faces in order, frame by frame; empty ones left out."""
