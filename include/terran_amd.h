@@ -305,6 +305,68 @@ typedef struct ta_saturate_region {
 } ta_saturate_region;
 int ta_frames_saturate(ta_ctx* ctx, ta_frames* frames, const ta_saturate_region* regions, int n);
 
+/* ---- neighbourhood filters: convolution kernels, rank filters, unsharp mask ----------------- */
+/* Filters regions of `frames` in place, Pillow's
+ *     im.paste(im.crop(box).filter(F), box[, ellipse mask])
+ * bit for bit.  Regions are as ta_frames_blur takes them (a half-open box inside the frame, no side longer than 16384,
+ * TA_BLUR_BOX or TA_BLUR_ELLIPSE) plus `spec`, the index of the region's filter in `specs`.  The filter sees only the
+ * region's own pixels: its border rules apply at the region's border, never the frame's.  Regions of one frame apply in
+ * list order where they overlap (rounds of pairwise disjoint regions); regions of different frames may be interleaved.
+ * A filter reads neighbours that the same call overwrites, so every round is staged: the results of a round go to the
+ * region's packed image in the context's scratch and are copied into the frame under the shape afterwards (kernels,
+ * ranks), or the frame is written from a blurred copy in scratch (unsharp).  The result does not depend on the launch
+ * geometry.  n = 0: TA_OK.
+ *
+ * TA_FILTER_KERNEL   ImageFilter.Kernel((size, size), kernel, scale, offset) with size 3 or 5, and through it the ten
+ *   built-in filters.  r = size / 2.  A region narrower or shorter than `size` is left as it is, and the outer r pixels
+ *   of a region keep their values.  Elsewhere, per channel, in float32 with every multiply and add rounded on its own:
+ *       k[i] = kernel[i] / scale  and  ss = offset + 0.5f          (on the host: the device never sees `scale`)
+ *       kernel row j (j = 0 first) belongs to image row y + r - j  (the kernel is applied bottom-up)
+ *       row = p[x-r] k[j][0];  row = row + p[x-r+1] k[j][1]; ...   (left to right);   ss = ss + row
+ *       output: 0 if ss <= 0, 255 if ss >= 255, else (uint8)ss, truncated.
+ *   has_factor != 0: ImageEnhance.Sharpness' Image.blend(filtered, original, factor): t = f + factor (o - f), the
+ *   unfused float32 expression of ta_frames_saturate: truncated when 0 <= factor <= 1, clipped to 0 .. 255 first otherwise;
+ *   factor 0 gives the filtered pixel, factor 1 the original.
+ * TA_FILTER_RANK     ImageFilter.RankFilter(size, rank), and through it MinFilter, MedianFilter and MaxFilter: odd size
+ *   1 .. 7, 0 <= rank < size^2; per channel the rank-th smallest value of the size x size window, whose coordinates are
+ *   clamped to the region (edge replication): every pixel is filtered, in regions smaller than the window too.
+ * TA_FILTER_UNSHARP  ImageFilter.UnsharpMask(radius, percent, threshold): b = the region's Gaussian blur exactly as
+ *   ta_frames_blur computes it, d = in - b in integers; out = in when |d| <= threshold, otherwise
+ *   clip(in + d percent / 100) with C integer division (towards zero; the product is taken in 64 bits).
+ *
+ * TA_E_INVALID, before any pixel changes: everything ta_frames_blur refuses; a `spec` outside 0 .. n_specs - 1; an unknown
+ * kind; a kernel size other than 3 or 5; a kernel entry, offset or factor that is not finite; a scale that is 0 or not
+ * finite; a rank size that is even or outside 1 .. 7, or a rank outside 0 .. size^2 - 1; a radius that is negative, not
+ * finite or above 1024; a negative percent or threshold.  Every spec is checked, used or not. */
+#define TA_FILTER_KERNEL 0
+#define TA_FILTER_RANK 1
+#define TA_FILTER_UNSHARP 2
+typedef struct ta_filter_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  int32_t spec;          /* index into `specs`                        */
+} ta_filter_region;
+typedef struct ta_filter_spec {
+  int32_t kind;          /* TA_FILTER_*                               */
+  int32_t size;          /* KERNEL: 3 or 5; RANK: 1, 3, 5 or 7        */
+  int32_t rank;          /* RANK                                      */
+  int32_t has_factor;    /* KERNEL: blend the result with the original */
+  float kernel[25];      /* KERNEL: size x size entries, row by row as Pillow takes them */
+  float scale, offset;   /* KERNEL                                    */
+  float factor;          /* KERNEL with has_factor: ImageEnhance.Sharpness' */
+  float radius;          /* UNSHARP: GaussianBlur's                   */
+  int32_t percent, threshold; /* UNSHARP                              */
+} ta_filter_spec;
+int ta_frames_filter(ta_ctx* ctx, ta_frames* frames, const ta_filter_region* regions, int n, const ta_filter_spec* specs,
+                     int n_specs);
+/* HOST ONLY, no context: what ta_frames_filter derives before it launches anything.  rounds[i]: the round region i runs
+ * in, as ta_blur_plan's.  kernels[25 s .. 25 s + 24]: the normalised entries kernel[i] / scale of spec s, zeros behind
+ * size^2 and for a spec of another kind; offsets[s]: its offset + 0.5f (0 for another kind).  Any output may be NULL.
+ * Frame indices only group the regions here.  TA_E_INVALID: what ta_frames_filter refuses without looking at a frame. */
+int ta_filter_plan(const ta_filter_region* regions, int n, const ta_filter_spec* specs, int n_specs, int32_t* rounds,
+                   float* kernels, float* offsets);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

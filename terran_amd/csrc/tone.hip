@@ -21,6 +21,7 @@
 // The in-place kernels run in rounds of regions that are pairwise disjoint within their frame (region_rounds.h), one
 // launch per round.
 #include "ta_internal.h"
+#include "pixel_walk.h"
 #include "region_rounds.h"
 
 #include <math.h>
@@ -33,7 +34,7 @@
 
 namespace {
 
-constexpr int THREADS = 256, WAVE = 64, WAVES = THREADS / WAVE;
+constexpr int THREADS = 256, WAVE = WALK_WAVE, WAVES = THREADS / WAVE;
 constexpr int MAX_SIDE = 16384;            // of a region: 2^28 pixels at most, so a count fits uint32
 constexpr int STRIP_PIXELS = 16384;        // pixels of one workgroup's strip of rows (at least one row per wave)
 
@@ -50,31 +51,6 @@ struct tone_item {           // one workgroup's strip: rows start .. start + cou
 };
 
 __device__ inline uint32_t luma(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16; }
-
-// Image.blend(in1, in2, f) of one sample; `inside`: 0 <= f <= 1
-__device__ inline uint32_t blend(uint32_t in1, uint32_t in2, float f, bool inside) {
-  const float t = __fadd_rn((float)(int)in1, __fmul_rn(f, (float)((int)in2 - (int)in1)));
-  if (inside) return (uint32_t)(int)t & 255u;
-  if (t <= 0.f) return 0;
-  if (t >= 255.f) return 255;
-  return (uint32_t)(int)t;
-}
-
-// The lanes of a wave over the `npx` pixels at `p`: one(pixel address) for the head and the tail, four(address of three
-// aligned dwords) for the groups.  Pixel k starts at p + 3 k, which is a multiple of 4 when k = p mod 4 (3 * 3 = 1 mod 4).
-template <class P, class F1, class F4>
-__device__ inline void walk_row(P* p, int npx, int lane, F1 one, F4 four) {
-  const int head = min(npx, (int)((uintptr_t)p & 3)), groups = (npx - head) >> 2, rest = head + 4 * groups;
-  const int units = head + groups + (npx - rest);
-  for (int u = lane; u < units; u += WAVE) {
-    if (u < head)
-      one(p + 3 * u);
-    else if (u < head + groups)
-      four(p + 3 * (head + 4 * (u - head)));
-    else
-      one(p + 3 * (rest + (u - head - groups)));
-  }
-}
 
 // rows of the strip, wave by wave: body(first pixel of the row's span, pixels in it)
 template <class P, class F>

@@ -738,6 +738,169 @@ def solarize_frames(frames, threshold=128, ctx=None):
     return point_frames(frames, solarize_lut(threshold), ctx=ctx)
 
 
+# ---- neighbourhood filters: Image.filter --------------------------------------------------------------------------------
+# Pillow's ten built-in filters (ImageFilter.BLUR ... SMOOTH_MORE): name -> (size, scale, offset, kernel), kept here so
+# that the names work without Pillow
+FILTER_BUILTINS = {
+    'blur': (5, 16, 0, (1, 1, 1, 1, 1, 1, 0, 0, 0, 1, 1, 0, 0, 0, 1, 1, 0, 0, 0, 1, 1, 1, 1, 1, 1)),
+    'contour': (3, 1, 255, (-1, -1, -1, -1, 8, -1, -1, -1, -1)),
+    'detail': (3, 6, 0, (0, -1, 0, -1, 10, -1, 0, -1, 0)),
+    'edge_enhance': (3, 2, 0, (-1, -1, -1, -1, 10, -1, -1, -1, -1)),
+    'edge_enhance_more': (3, 1, 0, (-1, -1, -1, -1, 9, -1, -1, -1, -1)),
+    'emboss': (3, 1, 128, (-1, 0, 0, 0, 1, 0, 0, 0, 0)),
+    'find_edges': (3, 1, 0, (-1, -1, -1, -1, 8, -1, -1, -1, -1)),
+    'sharpen': (3, 16, 0, (-2, -2, -2, -2, 32, -2, -2, -2, -2)),
+    'smooth': (3, 13, 0, (1, 1, 1, 1, 5, 1, 1, 1, 1)),
+    'smooth_more': (5, 100, 0, (1, 1, 1, 1, 1, 1, 5, 5, 5, 1, 1, 5, 44, 5, 1, 1, 5, 5, 5, 1, 1, 1, 1, 1, 1)),
+}
+FILTER_GAUSSIAN = 3                     # a spec kind of this module only: filter_frames routes it to ta_frames_blur
+FILTER_RANK_LIMIT = 7                   # the largest window of ta_frames_filter's rank filter
+_SHAPES = {'box': lib.BLUR_BOX, 'ellipse': lib.BLUR_ELLIPSE}
+
+
+def _finite32(values, what, who):
+    try:
+        a = np.asarray(values, np.float64).astype(np.float32)
+    except (TypeError, ValueError):
+        a = np.float32(np.nan)
+    if not np.isfinite(a).all():
+        raise ValueError('%s: %s must be finite, got %r' % (who, what, values))
+    return a
+
+
+def kernel_spec(size, kernel, scale=None, offset=0, factor=None):
+    """`ImageFilter.Kernel((size, size), kernel, scale, offset)` as a lib.FILTER_SPEC_DT record: size 3 or 5, scale None:
+    the sum of the kernel.  `factor`: blend the filtered image with the original as `ImageEnhance.Sharpness` does
+    (`Image.blend(filtered, original, factor)`)."""
+    who = 'kernel_spec'
+    if isinstance(size, (tuple, list)):
+        if len(size) != 2 or size[0] != size[1]:
+            raise ValueError('%s: a square kernel of size 3 or 5, got %r' % (who, size))
+        size = size[0]
+    if size not in (3, 5) or len(kernel) != size * size:
+        raise ValueError('%s: a kernel of 3 x 3 or 5 x 5 entries, got size %r and %d entries' % (who, size, len(kernel)))
+    if scale is None:
+        scale = sum(kernel)
+    spec = np.zeros((), lib.FILTER_SPEC_DT)
+    spec['kind'], spec['size'] = lib.FILTER_KERNEL, size
+    spec['kernel'][:size * size] = _finite32(kernel, 'the kernel', who)
+    spec['scale'], spec['offset'] = _finite32(scale, 'scale', who), _finite32(offset, 'offset', who)
+    if spec['scale'] == 0:
+        raise ValueError('%s: scale (the sum of the kernel, if none is given) must not be 0' % who)
+    if factor is not None:
+        spec['has_factor'], spec['factor'] = 1, _factor(factor, who)
+    return spec
+
+
+def rank_spec(size, rank):
+    """`ImageFilter.RankFilter(size, rank)` as a lib.FILTER_SPEC_DT record: odd size 1 .. 7, 0 <= rank < size * size."""
+    ints = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (size, rank))
+    if not ints or size % 2 == 0 or not 1 <= size <= FILTER_RANK_LIMIT or not 0 <= rank < size * size:
+        raise ValueError('RankFilter(%r, %r): an odd size within 1 .. %d and 0 <= rank < size * size' % (size, rank, FILTER_RANK_LIMIT))
+    spec = np.zeros((), lib.FILTER_SPEC_DT)
+    spec['kind'], spec['size'], spec['rank'] = lib.FILTER_RANK, size, rank
+    return spec
+
+
+def unsharp_spec(radius=2, percent=150, threshold=3):
+    """`ImageFilter.UnsharpMask(radius, percent, threshold)` as a lib.FILTER_SPEC_DT record: a scalar radius 0 .. 1024,
+    integers percent >= 0 and threshold >= 0."""
+    who = 'UnsharpMask(%r, %r, %r)' % (radius, percent, threshold)
+    if isinstance(radius, (tuple, list)):
+        raise ValueError('%s: a radius per axis is not offered' % who)
+    ints = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 0 <= v < 2 ** 31 for v in (percent, threshold))
+    if not ints or not 0 <= _finite32(radius, 'radius', who) <= 1024:
+        raise ValueError('%s: a radius within 0 .. 1024 and integers percent >= 0, threshold >= 0' % who)
+    spec = np.zeros((), lib.FILTER_SPEC_DT)
+    spec['kind'], spec['radius'], spec['percent'], spec['threshold'] = lib.FILTER_UNSHARP, radius, percent, threshold
+    return spec
+
+
+def filter_spec(flt):
+    """What `Image.filter(flt)` takes -> a lib.FILTER_SPEC_DT record for `Frames.filter` / `filter_frames`.  `flt`: a Pillow
+    `ImageFilter` instance or built-in class -- `Kernel`, the ten built-ins (`BLUR`, `CONTOUR`, `DETAIL`, `EDGE_ENHANCE`,
+    `EDGE_ENHANCE_MORE`, `EMBOSS`, `FIND_EDGES`, `SHARPEN`, `SMOOTH`, `SMOOTH_MORE`), `RankFilter` / `MinFilter` /
+    `MedianFilter` / `MaxFilter` up to size 7, `UnsharpMask`, and `GaussianBlur` with a scalar radius (kind
+    FILTER_GAUSSIAN, which `filter_frames` routes to `ta_frames_blur`) -- or a built-in's lower-case name, which needs no
+    Pillow.  A record passes through.  ValueError, naming the filter, for what is not offered: `ModeFilter`, `BoxBlur`, a
+    radius per axis, `MultibandFilter`s such as `Color3DLUT`, rank sizes above 7."""
+    if isinstance(flt, np.ndarray) and flt.dtype == lib.FILTER_SPEC_DT and flt.shape == ():
+        return flt
+    if isinstance(flt, str):
+        if flt not in FILTER_BUILTINS:
+            raise ValueError('filter_spec: %r is not one of %s' % (flt, sorted(FILTER_BUILTINS)))
+        size, scale, offset, kernel = FILTER_BUILTINS[flt]
+        return kernel_spec(size, kernel, scale, offset)
+    if isinstance(flt, type):
+        try:
+            flt = flt()                                  # Image.filter does the same with a class
+        except TypeError:
+            raise ValueError('filter_spec: %s needs arguments: pass an instance' % flt.__name__) from None
+    names = [c.__name__ for c in type(flt).__mro__]
+    name = names[0]
+    if 'RankFilter' in names:
+        if flt.size > FILTER_RANK_LIMIT:
+            raise ValueError('filter_spec: %s of size %r: rank filters are offered up to size %d' % (name, flt.size, FILTER_RANK_LIMIT))
+        return rank_spec(flt.size, flt.rank)
+    if 'UnsharpMask' in names:
+        return unsharp_spec(flt.radius, flt.percent, flt.threshold)
+    if 'GaussianBlur' in names:
+        if isinstance(flt.radius, (tuple, list)):
+            raise ValueError('filter_spec: GaussianBlur(%r): a radius per axis is not offered' % (flt.radius,))
+        spec = np.zeros((), lib.FILTER_SPEC_DT)
+        spec['kind'], spec['radius'] = FILTER_GAUSSIAN, _finite32(flt.radius, 'radius', 'GaussianBlur')
+        if not 0 <= spec['radius'] <= 1024:
+            raise ValueError('filter_spec: GaussianBlur(%r): a radius within 0 .. 1024' % (flt.radius,))
+        return spec
+    if 'BuiltinFilter' in names and hasattr(flt, 'filterargs'):
+        size, scale, offset, kernel = flt.filterargs
+        return kernel_spec(size, kernel, scale, offset)
+    raise ValueError('filter_spec: %s is not offered (kernels of 3 x 3 and 5 x 5, rank filters up to size 7, UnsharpMask and '
+                     'GaussianBlur with one radius are)' % name)
+
+
+def filter_frames(frames, flt, boxes=None, shape='box', ctx=None):
+    """Pillow's `Image.filter(flt)` of every resident frame, in place (`ta_frames_filter`, one call per batch; a
+    `GaussianBlur`: `ta_frames_blur`); returns `frames`.  `frames`: a `lib.Frames` batch or a list of them; `flt`: what
+    `filter_spec` takes; `boxes`: None, or one half-open integer (x0, y0, x1, y1) per frame, as `histogram_frames` takes
+    them: `im.paste(im.crop(box).filter(flt), box)`, the filter seeing the box's own pixels only; `shape`: 'box', or
+    'ellipse' (only the ellipse Pillow draws into the box is replaced)."""
+    who = 'filter_frames'
+    if shape not in _SHAPES:
+        raise ValueError("%s: shape must be 'box' or 'ellipse', got %r" % (who, shape))
+    spec = filter_spec(flt)
+    batches, _ = _batches(frames, who)
+    for b, q in zip(batches, _frame_boxes(batches, boxes, who)):
+        if not len(q):
+            continue
+        if spec['kind'] == FILTER_GAUSSIAN:
+            regions = _regions(lib.BLUR_DT, q, _SHAPES[shape])
+            regions['radius'] = spec['radius']
+            b.blur(regions, ctx=ctx)
+        else:
+            b.filter(_regions(lib.FILTER_REGION_DT, q, _SHAPES[shape]), spec, ctx=ctx)
+    return frames
+
+
+def sharpness_frames(frames, factor, ctx=None):
+    """`ImageEnhance.Sharpness(im).enhance(factor)` of every resident frame, in place: each frame blended with its own
+    `SMOOTH`; 0 smooths, 1 leaves the frame as it is, 2 sharpens."""
+    size, scale, offset, kernel = FILTER_BUILTINS['smooth']
+    return filter_frames(frames, kernel_spec(size, kernel, scale, offset, factor=_factor(factor, 'sharpness_frames')), ctx=ctx)
+
+
+def unsharp_frames(frames, radius=2, percent=150, threshold=3, ctx=None):
+    """`im.filter(ImageFilter.UnsharpMask(radius, percent, threshold))` of every resident frame, in place."""
+    return filter_frames(frames, unsharp_spec(radius, percent, threshold), ctx=ctx)
+
+
+def median_frames(frames, size=3, ctx=None):
+    """`im.filter(ImageFilter.MedianFilter(size))` of every resident frame, in place: odd size up to 7."""
+    if isinstance(size, (int, np.integer)) and size > FILTER_RANK_LIMIT:
+        raise ValueError('median_frames: MedianFilter of size %r: rank filters are offered up to size %d' % (size, FILTER_RANK_LIMIT))
+    return filter_frames(frames, rank_spec(size, size * size // 2 if isinstance(size, (int, np.integer)) else size), ctx=ctx)
+
+
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}
 
 

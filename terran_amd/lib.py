@@ -62,6 +62,8 @@ SIGNATURES = {
     'ta_frames_histogram': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_frames_point': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     'ta_frames_saturate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
+    'ta_frames_filter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
+    'ta_filter_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -153,6 +155,31 @@ assert POINT_DT.itemsize == 28
 SATURATE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
                         ('factor', '<f4')])
 assert SATURATE_DT.itemsize == 28
+
+# ta_filter_region, ta_filter_spec (include/terran_amd.h) and the kinds TA_FILTER_*; shapes: BLUR_*
+FILTER_KERNEL, FILTER_RANK, FILTER_UNSHARP = 0, 1, 2
+FILTER_REGION_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                             ('spec', '<i4')])
+assert FILTER_REGION_DT.itemsize == 28
+FILTER_SPEC_DT = np.dtype([('kind', '<i4'), ('size', '<i4'), ('rank', '<i4'), ('has_factor', '<i4'), ('kernel', '<f4', (25,)),
+                           ('scale', '<f4'), ('offset', '<f4'), ('factor', '<f4'), ('radius', '<f4'), ('percent', '<i4'),
+                           ('threshold', '<i4')])
+assert FILTER_SPEC_DT.itemsize == 140
+
+
+def filter_plan(regions, specs):
+    """Host only (no context, no device): ta_filter_plan -> (round of every region, float32 (n_specs, 25) normalised
+    kernels kernel / scale, float32 (n_specs,) offsets offset + 0.5): what ta_frames_filter derives from a FILTER_REGION_DT
+    and a FILTER_SPEC_DT array before it launches anything; zeros for the specs that are no kernels."""
+    lib = load()
+    regions = np.ascontiguousarray(regions, dtype=FILTER_REGION_DT)
+    specs = np.ascontiguousarray(specs, dtype=FILTER_SPEC_DT).reshape(-1)
+    n, m = len(regions), len(specs)
+    rounds, kernels, offsets = np.zeros(n, np.int32), np.zeros((m, 25), np.float32), np.zeros(m, np.float32)
+    rc = lib.ta_filter_plan(ptr(regions) if n else None, n, ptr(specs) if m else None, m, ptr(rounds), ptr(kernels), ptr(offsets))
+    if rc != OK:
+        raise TerranAmdError(rc, 'filter_plan: a bad box, shape or spec index, or a spec ta_frames_filter refuses')
+    return rounds, kernels, offsets
 
 
 def resample_filter(resample):
@@ -653,6 +680,17 @@ class Frames:
         ctx = ctx or self.ctx
         regions = np.ascontiguousarray(regions, dtype=SATURATE_DT)
         ctx.check(ctx.lib.ta_frames_saturate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+
+    def filter(self, regions, specs, ctx=None):
+        """Filter `regions` (a FILTER_REGION_DT array, in order) of this batch in place (ta_frames_filter): Pillow's
+        `crop(box).filter(F)` of each half-open box, pasted back under its shape; F is specs[region['spec']] (a
+        FILTER_SPEC_DT array: a convolution kernel, a rank filter or an unsharp mask; terran_amd.image.filter_spec makes
+        one from a Pillow filter).  `ctx`: the CALLER's, as in `blur`."""
+        ctx = ctx or self.ctx
+        regions = np.ascontiguousarray(regions, dtype=FILTER_REGION_DT)
+        specs = np.ascontiguousarray(specs, dtype=FILTER_SPEC_DT).reshape(-1)
+        ctx.check(ctx.lib.ta_frames_filter(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions),
+                                           ptr(specs) if len(specs) else None, len(specs)))
 
     def transform(self, regions, out_h, out_w, filter, fill=None, ctx=None):
         """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), method, a,

@@ -563,6 +563,29 @@ def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ct
     return frames
 
 
+def pack_filter(faces_per_frame, shapes, margin=0.0, shape='box'):
+    """-> lib.FILTER_REGION_DT array: pack_blur's regions (the same margin, truncation, clipping and order) for
+    Frames.filter, every one with spec 0.  Host only."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    rows = [(f, x0, y0, x1, y1, BLUR_SHAPES[shape], 0) for f, _, x0, y0, x1, y1 in _clipped_boxes(faces_per_frame, shapes, margin)]
+    return np.array(rows, lib.FILTER_REGION_DT)
+
+
+def filter_faces(frames, faces_per_frame, flt, margin=0.0, shape='box', ctx=None):
+    """Filter the faces of the resident batch `frames` (lib.Frames) in place, Pillow's `crop(box).filter(flt)` pasted back
+    under `shape`: sharpen soft faces before they are cropped, denoise them, take their edges.  The boxes, their clipping
+    and their order are blur_faces'; `flt`: what `image.filter_spec` takes (a GaussianBlur goes the way of blur_faces)."""
+    from . import image
+    _check_batch(frames, faces_per_frame)
+    spec = image.filter_spec(flt)
+    if spec['kind'] == image.FILTER_GAUSSIAN:
+        frames.blur(pack_blur(faces_per_frame, frames.shape, float(spec['radius']), margin, shape), ctx=ctx)
+    else:
+        frames.filter(pack_filter(faces_per_frame, frames.shape, margin, shape), spec, ctx=ctx)
+    return frames
+
+
 def anonymize_faces(image, faces, radius=None, margin=0.0, shape='box', method='gaussian', block=None):
     """A copy of the host image (uint8 (H, W, 3)) with every face (dict or list of dicts, face_tracking's included)
     blurred: Pillow's crop / GaussianBlur(radius) / paste of each box, or with method='pixelate' its crop / resize(BOX) /
