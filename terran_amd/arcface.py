@@ -169,7 +169,7 @@ class ArcFace(runtime.RangeFallback):
             model.h, frames.h, lib.ptr(idx), lib.ptr(mats), n, int(normalize), lib.ptr(out), lib.ptr(crops))))
         return (out, crops) if return_crops else out
 
-    def embed_faces_multi(self, frames_list, source_index, frame_index, matrices, normalize=True):
+    def embed_faces_multi(self, frames_list, source_index, frame_index, matrices, normalize=True, return_crops=False):
         """Faces cut from SEVERAL resident batches in one launch: face k comes from frames_list[source_index[k]], image
         frame_index[k] of it (ta_arcface_embed_faces_multi)."""
         import ctypes
@@ -178,10 +178,12 @@ class ArcFace(runtime.RangeFallback):
         mats = np.ascontiguousarray(matrices, dtype=np.float64).reshape(-1, 6)
         n = idx.shape[0]
         out = np.empty((n, 512), np.float32)
+        crops = np.empty((n, 3, 112, 112), np.uint8) if return_crops else None
         handles = (ctypes.c_void_p * len(frames_list))(*[f.h for f in frames_list])
         self._with_fallback(lambda model: self.ctx.check(self.ctx.lib.ta_arcface_embed_faces_multi(
-            model.h, handles, len(frames_list), lib.ptr(src), lib.ptr(idx), lib.ptr(mats), n, int(normalize), lib.ptr(out), None)))
-        return out
+            model.h, handles, len(frames_list), lib.ptr(src), lib.ptr(idx), lib.ptr(mats), n, int(normalize), lib.ptr(out),
+            lib.ptr(crops))))
+        return (out, crops) if return_crops else out
 
     def call_multi(self, items):
         """items: [(lib.Frames, faces_per_image), ...] -> [what `call(frames, faces_per_image)` returns, ...], all faces of
