@@ -1,0 +1,233 @@
+"""CPU tests (no GPU): the programs of tests/exact_programs.py are what tests/test_gpu_layers_exact.py takes them for.
+
+- their float64 reference equals torch-CPU float64 conv2d / max_pool2d (floor) / slicing on every builder and shape the GPU
+  module runs;
+- the exactness rule (16 significant bits; 2^24 for float32-only outputs) holds for all of them, and `reference` does refuse
+  a program that breaks it;
+- the packer really stores the operands of the depthwise / pool / copy cases as float32, bf16 pairs and half-float pairs in
+  the three precisions (a later packer change must not quietly turn these into float32-only tests), gives both sides of every
+  pool and copy one exponent, and keeps every tensor of the half-float mode inside the half-float range: a TA_E_RANGE on the
+  GPU would be a mistake of the test, not a finding;
+- the loader's program check accepts every program.
+"""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from terran_amd import lib, pack
+from tests import exact_programs as ep
+
+FMT_OF = {'f32': pack.FMT_F32, 'bf16x3': pack.FMT_SPLIT, 'f16x3': pack.FMT_SPLIT16}
+
+
+def torch_replay(net, fr):
+    """The same recipe on torch-CPU float64 ops."""
+    x0 = torch.zeros((fr.shape[0], 4) + fr.shape[1:3], dtype=torch.float64)
+    x0[:, :3] = torch.from_numpy(fr.astype(np.float64)).permute(0, 3, 1, 2).flip(1)
+    t = {'input': x0}
+    T = lambda a: torch.from_numpy(np.asarray(a, np.float64))
+    for op, src, dst, a in net.steps:
+        x = t[src]
+        if op == 'conv':
+            y = F.conv2d(x[:, :a['W'].shape[1]], T(a['W']), T(a['b']), stride=a['stride'], padding=a['pad'])
+            y = F.relu(y) if a['relu'] else y
+            y = F.max_pool2d(y, 2, 2) if a['pool'] else y
+        elif op == 'dwconv':
+            C = a['W'].shape[0]
+            y = F.conv2d(x[:, :C], T(a['W']), T(a['b']), stride=a['stride'], padding=1, groups=C)
+            y = F.relu(y) if a['relu'] else y
+        elif op == 'maxpool':
+            y = F.max_pool2d(x, 2, 2)
+        elif op == 'copych':
+            y = t[dst].clone()
+            y[:, a['out_off']:a['out_off'] + a['ch']] = x[:, a['in_off']:a['in_off'] + a['ch']]
+        elif op == 'dwpw':
+            C = a['Wd'].shape[0]
+            mid = F.relu(F.conv2d(x[:, :C], T(a['Wd']), T(a['bd']), stride=a['stride'], padding=1, groups=C))
+            t[dst + ':mid'] = mid
+            y = F.relu(F.conv2d(mid, T(a['Wp']), T(a['bp'])))
+        elif op == 'rfstem':
+            (Ws, bs), rest = a['blocks'][0], a['blocks'][1:]
+            y = F.relu(F.conv2d(x[:, :3], T(Ws), T(bs), stride=2, padding=1))
+            for i, (Wd, bd, Wp, bp) in enumerate(rest):
+                y = F.relu(F.conv2d(y, T(Wd), T(bd), stride=1 + i, padding=1, groups=Wd.shape[0]))
+                y = F.relu(F.conv2d(y, T(Wp), T(bp)))
+        t[dst] = y
+    return {k: v.numpy() for k, v in t.items()}
+
+
+def check(net, shapes, n=2, seed=100):
+    """Reference == torch on every shape, and what the half-float mode stores stays in its range.  -> the last reference."""
+    lib.check_program(net.P)                                       # packs the program: net.P.scales / mid_scales exist from here on
+    for h, w in shapes:
+        fr = ep.frames(seed + h * 31 + w, n, h, w)
+        ref = ep.reference(net, fr)
+        want = torch_replay(net, fr)
+        assert set(ref) == set(want)
+        for k in ref:
+            assert ref[k].shape == want[k].shape and np.array_equal(ref[k], want[k]), (k, h, w)
+        if net.precision == 'f16x3':
+            for name, tid in net.tid.items():
+                if name in ref and (net.read_by_an_op(name) or tid not in net.P.f32_only):
+                    in_half_range(ref[name], net.P.scales[tid], name)
+            for name, oi in net.mid_ops.items():
+                in_half_range(ref[name + ':mid'], net.P.mid_scales[oi], name + ':mid')
+    return ref
+
+
+def in_half_range(v, a, what):
+    """Integers stored times 2^a[c] as a half-float pair: the largest fits, and the lowest bit (2^a) is no subnormal's."""
+    top = np.abs(v).max(axis=(0, 2, 3)) * np.ldexp(1.0, a[:v.shape[1]].astype(np.int32))
+    assert top.max() <= ep.F16_MAX and a.min() >= -24, (what, float(top.max()), int(a.min()))
+
+
+def formats(net):
+    f = net.P.tensor_formats()
+    return {name: f[t] for name, t in net.tid.items()}
+
+
+@pytest.mark.parametrize('precision', ep.PRECISIONS)
+@pytest.mark.parametrize('C', ep.DW_CHANNELS)
+def test_dwconv_programs(precision, C):
+    net = ep.dwconv_net(precision, C)
+    ref = check(net, ep.DW_SHAPES)
+    f = formats(net)
+    names = ['dw_s%d_r%d' % v for v in ep.DW_VARIANTS]
+    for name in names + (['src'] if C else []):
+        assert f[name] == (FMT_OF[precision] if C % 32 == 0 and C else pack.FMT_F32), (name, f)
+    # the weights have negative taps: the ReLU matters, and what is kept uses the lo words of both pair formats
+    assert ref['dw_s1_r0'].min() < 0 and np.array_equal(ref['dw_s1_r1'], np.maximum(ref['dw_s1_r1'], 0))
+    if C >= 32:
+        assert _needs_lo(ref['src']) and _needs_lo(ref['dw_s1_r0'])
+    assert all(np.all(net.P.tensor_scales()[net.tid[k]] == 0) for k in names)        # plain depthwise tensors are stored unscaled
+
+
+def _needs_lo(v):
+    """Some value has more than the 11 bits of a half float's hi word (so more than the 8 of a bf16's as well)."""
+    v = np.abs(v[v != 0]).astype(np.int64)
+    return bool(np.any(v // (v & -v) >= 2048))
+
+
+@pytest.mark.parametrize('precision', ep.PRECISIONS)
+@pytest.mark.parametrize('in_halo', [0, 1])
+@pytest.mark.parametrize('C', ep.POOL_CHANNELS)
+def test_maxpool_programs(precision, C, in_halo):
+    net = ep.maxpool_net(precision, C, in_halo)
+    ref = check(net, ep.POOL_SHAPES)
+    f = formats(net)
+    src = 'input' if C == 4 else 'src'
+    want = FMT_OF[precision] if C % 32 == 0 else pack.FMT_F32
+    assert f[src] == want and f['pooled'] == want, f
+    assert net.P.tensors[net.tid[src]][1] == in_halo and net.P.tensors[net.tid['pooled']][1] == 1
+    s = net.P.tensor_scales()
+    assert np.array_equal(s[net.tid[src]], s[net.tid['pooled']])
+    if C != 4:
+        assert (ref['pooled'].max(axis=(0, 2, 3)) < 0).any()       # all-negative windows (11 x 13 frames): a max that starts at 0 shows
+        assert _needs_lo(ref['pooled'])
+    if C != 4 and precision == 'f16x3':                             # the shared exponent is the pinned one, not a second estimate
+        natural = ep.maxpool_net(precision, C, in_halo)
+        natural.P.forced_scale.clear()
+        assert np.all(s[net.tid['pooled']] == ep.PINNED_EXPONENT) and np.any(natural.P.tensor_scales()[net.tid['pooled']] != ep.PINNED_EXPONENT)
+
+
+@pytest.mark.parametrize('precision', ep.PRECISIONS)
+@pytest.mark.parametrize('case', sorted(ep.COPY_CASES))
+def test_copych_programs(precision, case):
+    c_src, c_dst, in_off, out_off, ch = ep.COPY_CASES[case][:5]
+    net = ep.copych_net(precision, *ep.COPY_CASES[case])
+    ref = check(net, ep.COPY_SHAPES)
+    f = formats(net)
+    whole_blocks = (in_off | out_off | ch) % 32 == 0
+    assert (case == 'offset4_falls_back_to_f32') == (not whole_blocks)
+    want = FMT_OF[precision] if whole_blocks else pack.FMT_F32
+    assert f['src'] == want and f['dst'] == want, f
+    s = net.P.tensor_scales()
+    assert np.array_equal(s[net.tid['src']][in_off:in_off + ch], s[net.tid['dst']][out_off:out_off + ch])
+    if precision == 'f16x3':
+        outside = np.r_[0:out_off, out_off + ch:c_dst]                 # ... the source's pinned one; the other channels keep theirs
+        assert np.all(s[net.tid['dst']][out_off:out_off + ch] == ep.PINNED_EXPONENT) and np.any(s[net.tid['dst']][outside] != ep.PINNED_EXPONENT)
+    # the copy changes the destination, and only there
+    before = ep.conv_ref(ref['input'], net.steps[0][3]['W'], net.steps[0][3]['b'], 1, 1)
+    keep = np.ones(c_dst, bool)
+    keep[out_off:out_off + ch] = False
+    assert np.array_equal(ref['dst'][:, keep], before[:, keep]) and not np.array_equal(ref['dst'], before)
+    assert _needs_lo(ref['src'])
+
+
+@pytest.mark.parametrize('precision', ep.PRECISIONS)
+def test_convpool_program(precision):
+    net = ep.convpool_net(precision)
+    ref = check(net, ep.CONVPOOL_SHAPES)
+    assert np.array_equal(ref['fused'], ref['pooled']) and ref['fused'].max() > 2048
+    f = formats(net)
+    assert f['src'] == FMT_OF[precision] and f['full'] == FMT_OF[precision] and f['fused'] == f['pooled'] == pack.FMT_F32
+    s = net.P.tensor_scales()
+    assert np.array_equal(s[net.tid['full']], s[net.tid['pooled']])
+
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x3'])
+@pytest.mark.parametrize('C,cout,stride', ep.DWPW_CASES)
+def test_dwpw_programs(precision, C, cout, stride):
+    net = ep.dwpw_net(precision, C, cout, stride)
+    ref = check(net, ep.DWPW_SHAPES)
+    assert formats(net)['src'] == pack.FMT_F32
+    assert ref['block'].max() > 2048 and (ref['block'] == 0).any() and (ref['block:mid'] == 0).any()      # both ReLUs cut something
+
+
+@pytest.mark.parametrize('fused', [False, True])
+def test_rfstem_programs(fused):
+    net = ep.rfstem_net('f32', fused)
+    lib.check_program(net.P)
+    for n, h, w in ep.RFSTEM_SHAPES:
+        fr = ep.frames(50 + h, n, h, w)
+        ref, want = ep.reference(net, fr), torch_replay(net, fr)
+        assert np.array_equal(ref['front'], want['front'])
+        q = 4 if fused else 2
+        assert ref['front'].shape == (n, 32 if fused else 16, (h + q - 1) // q, (w + q - 1) // q)
+        assert (ref['front'] > 0).mean() > 0.3                      # the ReLUs leave most of the map alive
+    assert ref['front'].max() > 1 << 12
+
+
+def test_second_trip_programs():
+    for k, (hw, total) in ep.SECOND_TRIP.items():
+        assert ep.GRID_CAP < total < ep.GRID_CAP * 1.02, k
+    h, w = ep.SECOND_TRIP['dwconv'][0]
+    net = ep.dwconv_net('f32', 32, variants=((1, 1),))
+    assert ep.reference(net, ep.frames(1, 1, h, w))['dw_s1_r1'][0, 0].size * 8 == ep.SECOND_TRIP['dwconv'][1]
+    h, w = ep.SECOND_TRIP['maxpool'][0]
+    net = ep.maxpool_net('f32', 64, 0, with_sink=False)
+    assert ep.reference(net, ep.frames(1, 1, h, w))['pooled'][0, 0].size * 16 == ep.SECOND_TRIP['maxpool'][1]
+    h, w = ep.SECOND_TRIP['copych'][0]
+    net = ep.copych_net('f32', 32, 64, 0, 0, 32, with_sink=False)
+    assert ep.reference(net, ep.frames(1, 1, h, w))['src'][0, 0].size * 8 == ep.SECOND_TRIP['copych'][1]
+    for net in (ep.dwconv_net('f32', 32, variants=((1, 1),)), ep.maxpool_net('f32', 64, 0, with_sink=False),
+                ep.copych_net('f32', 32, 64, 0, 0, 32, with_sink=False)):
+        check(net, [(6, 5)])
+
+
+@pytest.mark.parametrize('kind', [pack.MODEL_RETINAFACE, pack.MODEL_OPENPOSE, pack.MODEL_ARCFACE])
+def test_preprocess_programs_load(kind):
+    lib.check_program(ep.preprocess_net(kind).P)
+    fr = ep.frames(3, 1, 17, 23)
+    assert set(np.unique(fr)) == set(range(256))                    # every byte value occurs
+    x = ep.input_ref(fr)
+    assert np.array_equal(x[0, :3, 4, 5], fr[0, 4, 5, ::-1]) and not x[:, 3].any()
+
+
+def test_the_reference_refuses_what_is_not_exact():
+    """17 significant bits in a tensor the packer may split, and 2^24 in a float32 one."""
+    fr = np.full((1, 5, 5, 3), 255, np.uint8)
+    net = ep.Net('bf16x3')
+    net.tensor('big', 32, 0)
+    net.conv('input', 'big', np.full((32, 3, 1, 1), 90.0), np.zeros(32))              # 3 * 90 * 255 = 68850 >= 2^16
+    with pytest.raises(AssertionError, match='not exact'):
+        ep.reference(net, fr)
+    net = ep.Net('f32')
+    net.tensor('big', 32, 0, f32=True)
+    net.conv('input', 'big', np.full((32, 3, 1, 1), 90.0), np.zeros(32))              # float32 only and read by nothing: fine
+    ep.reference(net, fr)
+    net.tensor('bigger', 32, 0, f32=True)
+    net.conv('big', 'bigger', np.full((32, 32, 1, 1), 8.0), np.zeros(32))             # ... but now it is read (and 'bigger' passes 2^24)
+    with pytest.raises(AssertionError, match='not exact'):
+        ep.reference(net, fr)
