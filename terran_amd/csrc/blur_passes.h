@@ -16,17 +16,11 @@
 //              the blurred value, or under UNSHARP libImaging's UnsharpMask of the frame's own value and the blurred one.
 // A thread owns a chunk of consecutive outputs of one line and slides the window sum along it: two LDS reads per output
 // after the first.  Every output of a pass depends only on the pass's input buffer, so the result does not depend on
-// the launch geometry.  The ellipse mask is TA_DRAW_DISC's span table (ta_disc_rows, draw.hip).
+// the launch geometry.  The ellipse mask is TA_DRAW_DISC's span table (ta_span_tables, frame_regions.h).
 #pragma once
-#include "ta_internal.h"
+#include "frame_regions.h"
 
 #include <math.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <utility>
-#include <vector>
 
 namespace {
 namespace gauss {
@@ -134,6 +128,7 @@ __global__ __launch_bounds__(THREADS) void blur_cols(uint8_t* __restrict__ frame
   uint8_t* dst = frames + (((size_t)q.frame * H + q.y0) * (size_t)W + q.x0 + it.start) * 3;
   for (int i = threadIdx.x; i < bytes; i += THREADS) {
     const int row = i / pitch, c = i % pitch, px = it.start + c / 3;
+    // the span is clamped to the box on the host (ta_span_tables); px is in 0 .. w - 1 anyway, so that changes nothing here
     const int2 span = q.tab >= 0 ? tabs[q.tab + row] : make_int2(0, q.w - 1);
     if (px < span.x || px > span.y) continue;
     uint8_t* d = dst + (size_t)row * W * 3 + c;
@@ -177,10 +172,9 @@ struct blur_launch {
 struct blur_work {
   std::vector<blur_rec> recs;
   std::vector<blur_item> items;
-  std::vector<int2> tab;
+  ta_span_tables spans;
   std::vector<blur_launch> launches;
   size_t pixels = 0;
-  std::map<std::pair<int, int>, int> tab_of;
 
   // records, strips and the pixel scratch of one round: `jobs` are pairwise disjoint within their frame
   void add_round(const std::vector<blur_job>& jobs) {
@@ -198,15 +192,7 @@ struct blur_work {
       box_params(q.radius, &fr, &r.r, &r.ww, &r.fw);
       r.percent = q.percent;
       r.threshold = q.threshold;
-      r.tab = -1;
-      if (q.shape == TA_BLUR_ELLIPSE) {
-        auto it = tab_of.find({r.w, r.h});
-        if (it == tab_of.end()) {
-          it = tab_of.emplace(std::make_pair(r.w, r.h), (int)tab.size()).first;
-          ta_disc_rows(r.w - 1, r.h - 1, tab);            // rows 0 .. h - 1 of ellipse([0, 0, w - 1, h - 1])
-        }
-        r.tab = it->second;
-      }
+      r.tab = q.shape == TA_BLUR_ELLIPSE ? spans.of(r.w, r.h) : -1;
       r.scratch = at;
       at += ((size_t)r.w * r.h * 3 + 15) & ~(size_t)15;
       recs.push_back(r);
@@ -231,17 +217,23 @@ struct blur_work {
     L.cols = (int)items.size() - L.col0;
     launches.push_back(L);
   }
-};
 
-// the two launches of one round; the records, strips, tables and the pixel scratch are on the device
-template <bool UNSHARP>
-void launch_round(hipStream_t stream, uint8_t* frames, int H, int W, const blur_launch& L, const blur_rec* recs, const blur_item* items,
-                  const int2* tabs, uint8_t* pixels) {
-  if (!L.rows) return;
-  hipLaunchKernelGGL(blur_rows, dim3(L.rows), dim3(THREADS), L.row_lds, stream, (const uint8_t*)frames, H, W, recs, items + L.row0, pixels);
-  hipLaunchKernelGGL(blur_cols<UNSHARP>, dim3(L.cols), dim3(THREADS), L.col_lds, stream, frames, H, W, recs, items + L.col0, tabs,
-                     (const uint8_t*)pixels);
-}
+  // records, strips and span tables into the call's staging (frame_regions.h)
+  size_t o_rec = 0, o_item = 0, o_tab = 0;
+  void put(ta_staging& st) { o_rec = st.put(recs), o_item = st.put(items), o_tab = st.put(spans.table()); }
+
+  // the two launches of round k, after the staging's commit; `pixels`: the pixel scratch on the device
+  template <bool UNSHARP>
+  void launch_round(hipStream_t stream, uint8_t* frames, int H, int W, size_t k, const ta_staging& st, uint8_t* pixels) const {
+    const blur_launch& L = launches[k];
+    if (!L.rows) return;
+    const blur_rec* d_recs = st.dev<const blur_rec>(o_rec);
+    const blur_item* d_items = st.dev<const blur_item>(o_item);
+    hipLaunchKernelGGL(blur_rows, dim3(L.rows), dim3(THREADS), L.row_lds, stream, (const uint8_t*)frames, H, W, d_recs, d_items + L.row0, pixels);
+    hipLaunchKernelGGL(blur_cols<UNSHARP>, dim3(L.cols), dim3(THREADS), L.col_lds, stream, frames, H, W, d_recs, d_items + L.col0,
+                       st.dev<const int2>(o_tab), (const uint8_t*)pixels);
+  }
+};
 
 }  // namespace gauss
 }  // namespace

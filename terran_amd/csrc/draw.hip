@@ -11,15 +11,9 @@
 // only ever read and written by one lane, in primitive order: the result does not depend on the launch geometry, and no
 // pixel outside a primitive's spans is touched.  Compiled with -ffp-contract=off (build.py): the polygon scan's float
 // arithmetic must round as Pillow's C does.
-#include "ta_internal.h"
+#include "frame_regions.h"
 
 #include <math.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <utility>
-#include <vector>
 
 namespace {
 
@@ -334,8 +328,7 @@ void disc_rows(int a, int b, std::vector<int2>& tab) {
 // both entry points; `with_masks`: TA_DRAW_MASK is a known kind and `masks` (mask_bytes bytes, may be NULL) holds the bitmaps
 int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool with_masks, const uint8_t* masks,
          size_t mask_bytes) {
-  if (!frames || n < 0 || (n > 0 && !prims)) return ta_fail(ctx, TA_E_INVALID, "frames_draw: bad args");
-  if (frames->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_draw: the batch lives on another device");
+  TA_TRY(ta_check_batch(ctx, "frames_draw", frames, prims, n));
   const int N = frames->n, H = frames->h, W = frames->w;
   const int LIM = 1 << 24;
   for (int i = 0; i < n; ++i) {
@@ -371,8 +364,7 @@ int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool 
 
   std::vector<draw_rec> recs(n);
   std::vector<int2> yb(n);
-  std::vector<int2> tab;
-  std::map<std::pair<int, int>, int> tab_of;
+  ta_span_tables spans(false);                          // relative to the primitive's corner, not clamped: the kernel clips
   for (int k = 0; k < n; ++k) {
     const ta_draw_prim& q = prims[order[k]];
     draw_rec& r = recs[k];
@@ -397,15 +389,10 @@ int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool 
       if (q.x1 < 0 || q.x0 >= W) ylo = 1, yhi = 0;
     } else if (q.kind == TA_DRAW_DISC) {
       const int a = q.x1 - q.x0, b = q.y1 - q.y0;
-      auto it = tab_of.find({a, b});
-      if (it == tab_of.end()) {
-        it = tab_of.emplace(std::make_pair(a, b), (int)tab.size()).first;
-        disc_rows(a, b, tab);
-      }
       r.kind = K_DISC;
       r.v[0] = q.x0;
       r.v[1] = q.y0;
-      r.v[2] = it->second;
+      r.v[2] = spans.of(a + 1, b + 1);                  // ellipse([0, 0, a, b])
       ylo = q.y0;
       yhi = q.y1;
       if (a + b < 1) ylo = 1, yhi = 0;                 // Pillow draws nothing for a one-pixel box
@@ -443,27 +430,13 @@ int draw(ta_ctx* ctx, ta_frames* frames, const ta_draw_prim* prims, int n, bool 
     }
     yb[k] = make_int2(std::max(ylo, 0), std::min(yhi, H - 1));
   }
-  if (tab.empty()) tab.push_back(make_int2(1, 0));
 
-  const size_t b_fs = fstart.size() * sizeof(int32_t), b_yb = (size_t)n * sizeof(int2), b_rec = (size_t)n * sizeof(draw_rec),
-               b_tab = tab.size() * sizeof(int2);
-  const size_t o_yb = (b_fs + 15) & ~(size_t)15, o_rec = (o_yb + b_yb + 63) & ~(size_t)63, o_tab = o_rec + b_rec;
-  const size_t o_mask = o_tab + b_tab, b_mask = masks ? mask_bytes : 0;
-  const size_t total = o_mask + b_mask;
-  void *scr = nullptr, *pin = nullptr;
-  TA_TRY(ta_scratch(ctx, total, &scr));
-  TA_TRY(ta_pinned(ctx, total, &pin));
-  char* hp = (char*)pin;
-  memcpy(hp, fstart.data(), b_fs);
-  memcpy(hp + o_yb, yb.data(), b_yb);
-  memcpy(hp + o_rec, recs.data(), b_rec);
-  memcpy(hp + o_tab, tab.data(), b_tab);
-  if (b_mask) memcpy(hp + o_mask, masks, b_mask);
-  TA_HIP(ctx, hipMemcpyAsync(scr, pin, total, hipMemcpyHostToDevice, ctx->stream));
-  char* dp = (char*)scr;
-  hipLaunchKernelGGL(draw_kernel, dim3((H + 3) / 4, N), dim3(256), 0, ctx->stream, frames->dev, H, W, (const int32_t*)dp,
-                     (const int2*)(dp + o_yb), (const draw_rec*)(dp + o_rec), (const int2*)(dp + o_tab),
-                     (const uint8_t*)(dp + o_mask));
+  ta_staging st;                                        // one H2D copy; draw_kernel loads whole records: a 64-byte boundary
+  const size_t o_fs = st.put(fstart), o_yb = st.put(yb), o_rec = st.put(recs, 64), o_tab = st.put(spans.table(), 8);
+  const size_t o_mask = st.put(masks, masks ? mask_bytes : 0, 1);
+  TA_TRY(st.commit(ctx));
+  hipLaunchKernelGGL(draw_kernel, dim3((H + 3) / 4, N), dim3(256), 0, ctx->stream, frames->dev, H, W, st.dev<const int32_t>(o_fs),
+                     st.dev<const int2>(o_yb), st.dev<const draw_rec>(o_rec), st.dev<const int2>(o_tab), st.dev<const uint8_t>(o_mask));
   TA_HIP(ctx, hipGetLastError());
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call
   return TA_OK;

@@ -7,7 +7,7 @@
 // 0.5 to the offset (normalise): the device sees those float32 values only.
 //
 // A filter reads neighbours that the same call overwrites, so every round of regions that are pairwise disjoint within
-// their frame (region_rounds.h) runs in two launches:
+// their frame (frame_regions.h) runs in two launches:
 //   filter_tiles: a workgroup takes a TILE_W x TILE_H = 128 x 32 pixel tile of one region, loads it with a halo of
 //                 size / 2 pixels, clipped to the region, into LDS as bytes -- whole aligned dwords of the frame, so a row
 //                 sits in LDS at the byte phase (0 .. 3) it has in memory -- and every thread computes groups of four
@@ -23,18 +23,17 @@
 // UnsharpMask runs blur_passes.h's two launches, the last with its unsharp write.
 #include "blur_passes.h"
 #include "pixel_walk.h"
-#include "region_rounds.h"
+#include "frame_regions.h"
 
 namespace {
 
-constexpr int THREADS = 256, WAVE = WALK_WAVE, WAVES = THREADS / WAVE;
+constexpr int THREADS = WALK_THREADS;
 constexpr int MAX_SIDE = gauss::MAX_SIDE;
 constexpr int TILE_W = 128, TILE_H = 32, MAX_R = 3;       // pixels of a tile; the widest halo (rank size 7)
 constexpr int GROUPS = TILE_W / 4;                        // groups of four pixels in a tile row
 constexpr int TILE_ROWS = TILE_H + 2 * MAX_R;
 constexpr int PITCH = (3 + 3 * (TILE_W + 2 * MAX_R) + 3) & ~3;   // bytes of a tile row in LDS: phase, pixels, rounded up
 constexpr int PITCH_DW = PITCH / 4;
-constexpr int STRIP_PIXELS = 16384;                       // pixels of one filter_paste workgroup's strip of rows
 enum { BLEND_NONE = 0, BLEND_TRUNCATE = 1, BLEND_CLIP = 2 };
 
 struct filter_rec {          // 40 bytes
@@ -55,8 +54,8 @@ struct filter_dspec {        // 128 bytes: a spec as the device sees it
 };
 static_assert(sizeof(filter_dspec) == 128, "filter_dspec");
 
-struct filter_item {         // filter_tiles: the tile's first pixel (a, b) = (x, y) in the region; filter_paste: rows a .. a + b - 1
-  int32_t rec, a, b;
+struct filter_item {         // filter_tiles: the tile's first pixel (x, y) in the region
+  int32_t rec, x, y;
 };
 
 // the tile in LDS: rows ry0 .. of the region from pixel cx0 on, row r at byte phase (ph0 + r * phs) & 3
@@ -116,7 +115,7 @@ __device__ inline uint32_t rank_of(const tile_view& t, const filter_dspec& sp, i
 template <class F>
 __device__ inline void run_tile(const filter_item& it, const filter_rec& q, uint8_t* __restrict__ scratch, F sample) {
   for (int u = threadIdx.x; u < TILE_H * GROUPS; u += THREADS) {
-    const int y = it.b + u / GROUPS, x = it.a + 4 * (u % GROUPS);
+    const int y = it.y + u / GROUPS, x = it.x + 4 * (u % GROUPS);
     if (y >= q.h || x >= q.w) continue;
     uint32_t* dst = (uint32_t*)(scratch + q.scratch + (size_t)y * q.pitch + 3 * x);
 #pragma unroll 1
@@ -140,7 +139,7 @@ __global__ __launch_bounds__(THREADS) void filter_tiles(const uint8_t* __restric
   const filter_rec q = recs[it.rec];
   const filter_dspec sp = specs[q.spec];
   const int R = sp.size >> 1;
-  const int cx0 = max(it.a - R, 0), cx1 = min(it.a + TILE_W + R, q.w), ry0 = max(it.b - R, 0), ry1 = min(it.b + TILE_H + R, q.h);
+  const int cx0 = max(it.x - R, 0), cx1 = min(it.x + TILE_W + R, q.w), ry0 = max(it.y - R, 0), ry1 = min(it.y + TILE_H + R, q.h);
   const size_t row_bytes = (size_t)W * 3;
   const size_t off0 = (((size_t)q.frame * H + q.y0 + ry0) * (size_t)W + q.x0 + cx0) * 3;
   const int nbytes = 3 * (cx1 - cx0);
@@ -175,18 +174,14 @@ __global__ __launch_bounds__(THREADS) void filter_tiles(const uint8_t* __restric
 }
 
 __global__ __launch_bounds__(THREADS) void filter_paste(uint8_t* __restrict__ frames, int H, int W, const filter_rec* __restrict__ recs,
-                                                        const filter_item* __restrict__ items, const int2* __restrict__ tabs,
+                                                        const strip_item* __restrict__ items, const int2* __restrict__ tabs,
                                                         const uint8_t* __restrict__ scratch) {
-  const filter_item it = items[blockIdx.x];
+  const strip_item it = items[blockIdx.x];
   const filter_rec q = recs[it.rec];
-  const int wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
-  for (int r = it.a + wave; r < it.a + it.b; r += WAVES) {
-    const int2 span = q.tab >= 0 ? tabs[q.tab + r] : make_int2(0, q.w - 1);   // clamped to the box on the host
-    if (span.x > span.y) continue;
-    uint8_t* p = frames + (((size_t)q.frame * H + q.y0 + r) * (size_t)W + q.x0 + span.x) * 3;
-    const uint8_t* s = scratch + q.scratch + (size_t)r * q.pitch + 3 * span.x;
+  walk_strip(frames, H, W, q, it, tabs, [&](uint8_t* p, int npx, int r, int x) {
+    const uint8_t* s = scratch + q.scratch + (size_t)r * q.pitch + 3 * x;
     walk_row(
-        p, span.y - span.x + 1, lane,
+        p, npx, threadIdx.x % WALK_WAVE,
         [&](uint8_t* px) {
           const uint8_t* from = s + (px - p);
           px[0] = from[0], px[1] = from[1], px[2] = from[2];
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(THREADS) void filter_paste(uint8_t* __restrict__ fr
           d[1] = __builtin_amdgcn_alignbyte(d2, d1, m);
           d[2] = __builtin_amdgcn_alignbyte(d3, d2, m);
         });
-  }
+  });
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
@@ -227,13 +222,6 @@ const char* check_spec(const ta_filter_spec& s) {
   return "unknown kind";
 }
 
-const char* check_region(const ta_filter_region& q, int n_specs) {
-  if (q.x1 <= q.x0 || q.y1 <= q.y0) return "empty or inverted box";
-  if (q.shape != TA_BLUR_BOX && q.shape != TA_BLUR_ELLIPSE) return "unknown shape";
-  if (q.spec < 0 || q.spec >= n_specs) return "spec index out of range";
-  return nullptr;
-}
-
 // a spec as the device sees it: libImaging divides the float32 kernel by the float32 divisor and adds 0.5 to the offset
 void normalise(const ta_filter_spec& s, filter_dspec& d) {
   memset(&d, 0, sizeof(d));
@@ -253,56 +241,48 @@ bool idle(const ta_filter_region& q, const ta_filter_spec& s) {
 }
 
 struct filter_round {
-  int tile0 = 0, tiles = 0, strip0 = 0, strips = 0;   // the round's workgroups in `items`
+  int tile0 = 0, tiles = 0, strip0 = 0, strips = 0;   // the round's workgroups in `tiles` and `strips`
 };
 struct filter_work {
   std::vector<filter_rec> recs;
-  std::vector<filter_item> items;
-  std::vector<int2> tab;                              // every span clamped to its box
+  std::vector<filter_item> tiles;
+  std::vector<strip_item> strips;
+  ta_span_tables spans;
   std::vector<filter_round> rounds;
-  size_t pixels = 0;
-  std::map<std::pair<int, int>, int> tab_of;
+  size_t pixels = 0;                                  // the largest round's packed results
+  size_t closed = 0, at = 0;                          // records of the rounds closed so far; bytes of the open round
 
-  void add(const ta_filter_region& q, size_t* at) {
+  void add(const ta_filter_region& q) {
     filter_rec r;
     memset(&r, 0, sizeof(r));
     r.frame = q.frame, r.x0 = q.x0, r.y0 = q.y0, r.w = q.x1 - q.x0, r.h = q.y1 - q.y0;
     r.spec = q.spec;
-    r.tab = -1;
-    if (q.shape == TA_BLUR_ELLIPSE) {
-      auto it = tab_of.find({r.w, r.h});
-      if (it == tab_of.end()) {
-        const size_t first = tab.size();
-        it = tab_of.emplace(std::make_pair(r.w, r.h), (int)first).first;
-        ta_disc_rows(r.w - 1, r.h - 1, tab);                // rows 0 .. h - 1 of ellipse([0, 0, w - 1, h - 1])
-        tab.resize(first + r.h, make_int2(1, 0));
-        for (size_t k = first; k < tab.size(); ++k) tab[k] = make_int2(std::max(tab[k].x, 0), std::min(tab[k].y, r.w - 1));
-      }
-      r.tab = it->second;
-    }
+    r.tab = q.shape == TA_BLUR_ELLIPSE ? spans.of(r.w, r.h) : -1;
     r.pitch = 12 * ((r.w + 3) / 4);
-    r.scratch = *at;
-    *at += ((size_t)r.pitch * r.h + 15) & ~(size_t)15;
+    r.scratch = at;
+    at += ((size_t)r.pitch * r.h + 15) & ~(size_t)15;
     recs.push_back(r);
   }
-  // closes a round: the tiles and the strips of the records from `first` on
-  void close(size_t first, size_t at) {
+  // closes a round: the tiles and the strips of the records added since the last one
+  void close() {
     filter_round L;
-    L.tile0 = (int)items.size();
-    for (size_t j = first; j < recs.size(); ++j)
+    L.tile0 = (int)tiles.size();
+    for (size_t j = closed; j < recs.size(); ++j)
       for (int y = 0; y < recs[j].h; y += TILE_H)
-        for (int x = 0; x < recs[j].w; x += TILE_W) items.push_back({(int32_t)j, x, y});
-    L.tiles = (int)items.size() - L.tile0;
-    L.strip0 = (int)items.size();
-    for (size_t j = first; j < recs.size(); ++j) {
-      const int rows = std::max(WAVES, STRIP_PIXELS / recs[j].w);
-      for (int y = 0; y < recs[j].h; y += rows) items.push_back({(int32_t)j, y, std::min(rows, recs[j].h - y)});
-    }
-    L.strips = (int)items.size() - L.strip0;
+        for (int x = 0; x < recs[j].w; x += TILE_W) tiles.push_back({(int32_t)j, x, y});
+    L.tiles = (int)tiles.size() - L.tile0;
+    L.strip0 = (int)strips.size();
+    L.strips = ta_add_strips(strips, recs, closed, WALK_WAVES, STRIP_PIXELS);
     rounds.push_back(L);
     pixels = std::max(pixels, at);
+    closed = recs.size(), at = 0;
   }
 };
+
+// a region's own defect: its spec
+auto spec_in(int n_specs) {
+  return [n_specs](const ta_filter_region& q) { return q.spec < 0 || q.spec >= n_specs ? "spec index out of range" : (const char*)nullptr; };
+}
 
 }  // namespace
 
@@ -312,7 +292,7 @@ extern "C" int ta_filter_plan(const ta_filter_region* regions, int n, const ta_f
   for (int s = 0; s < n_specs; ++s)
     if (check_spec(specs[s])) return TA_E_INVALID;
   for (int i = 0; i < n; ++i)
-    if (check_region(regions[i], n_specs)) return TA_E_INVALID;
+    if (ta_region_defect(regions[i], spec_in(n_specs))) return TA_E_INVALID;
   std::vector<int32_t> round;
   ta_plan_rounds(regions, n, round);
   for (int i = 0; i < n && rounds; ++i) rounds[i] = round[i];
@@ -329,93 +309,58 @@ extern "C" int ta_frames_filter(ta_ctx* ctx, ta_frames* frames, const ta_filter_
                                 int n_specs) {
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
-  if (!frames || n < 0 || n_specs < 0 || (n > 0 && !regions) || (n_specs > 0 && !specs)) return ta_fail(ctx, TA_E_INVALID, "frames_filter: bad args");
-  if (frames->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_filter: the batch lives on another device");
-  const int N = frames->n, H = frames->h, W = frames->w;
+  if (n_specs < 0 || (n_specs > 0 && !specs)) return ta_fail(ctx, TA_E_INVALID, "frames_filter: bad args");
+  TA_TRY(ta_check_batch(ctx, "frames_filter", frames, regions, n));
   for (int s = 0; s < n_specs; ++s)
     if (const char* why = check_spec(specs[s])) return ta_fail(ctx, TA_E_INVALID, "frames_filter: spec %d: %s", s, why);
-  for (int i = 0; i < n; ++i) {
-    const ta_filter_region& q = regions[i];
-    if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "frames_filter: region %d: frame %d out of range [0, %d)", i, q.frame, N);
-    if (const char* why = check_region(q, n_specs)) return ta_fail(ctx, TA_E_INVALID, "frames_filter: region %d: %s", i, why);
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > W || q.y1 > H)
-      return ta_fail(ctx, TA_E_INVALID, "frames_filter: region %d: [%d, %d) x [%d, %d) is not inside the %d x %d frame", i, q.x0, q.x1, q.y0, q.y1, W, H);
-    if (q.x1 - q.x0 > MAX_SIDE || q.y1 - q.y0 > MAX_SIDE)
-      return ta_fail(ctx, TA_E_INVALID, "frames_filter: region %d: a side longer than %d", i, MAX_SIDE);
-  }
+  TA_TRY(ta_check_boxes(ctx, "frames_filter", frames, regions, n, MAX_SIDE, spec_in(n_specs)));
   if (n == 0) return TA_OK;
 
   // round by round: the kernel and rank regions of a round go through filter_tiles / filter_paste, its unsharp regions
   // through the blur passes; they are disjoint, so the order of the two within a round does not matter
-  std::vector<int32_t> round;
-  const int rounds = ta_plan_rounds(regions, n, round);
   filter_work fw;
   gauss::blur_work bw;
   std::vector<gauss::blur_job> jobs;
-  for (int k = 0; k < rounds; ++k) {
-    const size_t first = fw.recs.size();
-    size_t at = 0;
-    jobs.clear();
-    for (int i = 0; i < n; ++i) {
-      const ta_filter_region& q = regions[i];
-      const ta_filter_spec& s = specs[q.spec];
-      if (round[i] != k || idle(q, s)) continue;
-      if (s.kind == TA_FILTER_UNSHARP)
-        jobs.push_back({q.frame, q.x0, q.y0, q.x1, q.y1, q.shape, s.radius, s.percent, s.threshold});
-      else
-        fw.add(q, &at);
-    }
-    fw.close(first, at);
-    bw.add_round(jobs);
-  }
+  ta_each_round(
+      regions, n,
+      [&](const ta_filter_region& q) {
+        const ta_filter_spec& s = specs[q.spec];
+        if (idle(q, s)) return;
+        if (s.kind == TA_FILTER_UNSHARP)
+          jobs.push_back({q.frame, q.x0, q.y0, q.x1, q.y1, q.shape, s.radius, s.percent, s.threshold});
+        else
+          fw.add(q);
+      },
+      [&] {
+        fw.close();
+        bw.add_round(jobs);
+        jobs.clear();
+      });
   if (fw.recs.empty() && bw.recs.empty()) return TA_OK;
   std::vector<filter_dspec> dspecs(n_specs);
   for (int s = 0; s < n_specs; ++s) normalise(specs[s], dspecs[s]);
-  if (fw.tab.empty()) fw.tab.push_back(make_int2(1, 0));
-  if (bw.tab.empty()) bw.tab.push_back(make_int2(1, 0));
 
-  // one staging copy: the filter's records, specs, workgroups and spans, then the blur's; behind them the two pixel areas
-  size_t staged = 0;
-  auto place = [&](size_t bytes) {
-    const size_t o = staged;
-    staged = (staged + bytes + 15) & ~(size_t)15;
-    return o;
-  };
-  const size_t b_frec = fw.recs.size() * sizeof(filter_rec), b_spec = dspecs.size() * sizeof(filter_dspec);
-  const size_t b_fitem = fw.items.size() * sizeof(filter_item), b_ftab = fw.tab.size() * sizeof(int2);
-  const size_t b_brec = bw.recs.size() * sizeof(gauss::blur_rec), b_bitem = bw.items.size() * sizeof(gauss::blur_item);
-  const size_t b_btab = bw.tab.size() * sizeof(int2);
-  const size_t o_frec = place(b_frec), o_spec = place(b_spec), o_fitem = place(b_fitem), o_ftab = place(b_ftab);
-  const size_t o_brec = place(b_brec), o_bitem = place(b_bitem), o_btab = place(b_btab);
-  const size_t o_fpix = (staged + 255) & ~(size_t)255, o_bpix = (o_fpix + fw.pixels + 255) & ~(size_t)255;
-  void *scr = nullptr, *pin = nullptr;
-  TA_TRY(ta_scratch(ctx, o_bpix + bw.pixels, &scr));
-  TA_TRY(ta_pinned(ctx, staged, &pin));
-  char* hp = (char*)pin;
-  memcpy(hp + o_frec, fw.recs.data(), b_frec);
-  memcpy(hp + o_spec, dspecs.data(), b_spec);
-  memcpy(hp + o_fitem, fw.items.data(), b_fitem);
-  memcpy(hp + o_ftab, fw.tab.data(), b_ftab);
-  memcpy(hp + o_brec, bw.recs.data(), b_brec);
-  memcpy(hp + o_bitem, bw.items.data(), b_bitem);
-  memcpy(hp + o_btab, bw.tab.data(), b_btab);
-  TA_HIP(ctx, hipMemcpyAsync(scr, pin, staged, hipMemcpyHostToDevice, ctx->stream));
-  char* dp = (char*)scr;
-  const filter_rec* d_frec = (const filter_rec*)(dp + o_frec);
-  const filter_item* d_fitem = (const filter_item*)(dp + o_fitem);
-  const size_t total = (size_t)N * H * W * 3;
+  // one H2D copy: the filter's records, specs, workgroups and spans, then the blur's; behind them the two pixel areas
+  ta_staging st;
+  const size_t o_frec = st.put(fw.recs), o_spec = st.put(dspecs), o_tile = st.put(fw.tiles), o_strip = st.put(fw.strips);
+  const size_t o_ftab = st.put(fw.spans.table());
+  bw.put(st);
+  const size_t o_fpix = st.device_only(fw.pixels), o_bpix = st.device_only(bw.pixels);
+  TA_TRY(st.commit(ctx));
+  const filter_rec* d_frec = st.dev<const filter_rec>(o_frec);
+  const int H = frames->h, W = frames->w;
+  const size_t total = (size_t)frames->n * H * W * 3;
   TA_SET_LDS_ATTR(ctx, gauss::blur_rows, gauss::LDS_BUDGET);
   TA_SET_LDS_ATTR(ctx, gauss::blur_cols<true>, gauss::LDS_BUDGET);
-  for (int k = 0; k < rounds; ++k) {
+  for (size_t k = 0; k < fw.rounds.size(); ++k) {
     const filter_round& L = fw.rounds[k];
     if (L.tiles) {
       hipLaunchKernelGGL(filter_tiles, dim3(L.tiles), dim3(THREADS), 0, ctx->stream, (const uint8_t*)frames->dev, total, H, W, d_frec,
-                         (const filter_dspec*)(dp + o_spec), d_fitem + L.tile0, (uint8_t*)(dp + o_fpix));
-      hipLaunchKernelGGL(filter_paste, dim3(L.strips), dim3(THREADS), 0, ctx->stream, frames->dev, H, W, d_frec, d_fitem + L.strip0,
-                         (const int2*)(dp + o_ftab), (const uint8_t*)(dp + o_fpix));
+                         st.dev<const filter_dspec>(o_spec), st.dev<const filter_item>(o_tile) + L.tile0, st.dev<uint8_t>(o_fpix));
+      hipLaunchKernelGGL(filter_paste, dim3(L.strips), dim3(THREADS), 0, ctx->stream, frames->dev, H, W, d_frec,
+                         st.dev<const strip_item>(o_strip) + L.strip0, st.dev<const int2>(o_ftab), st.dev<const uint8_t>(o_fpix));
     }
-    gauss::launch_round<true>(ctx->stream, frames->dev, H, W, bw.launches[k], (const gauss::blur_rec*)(dp + o_brec),
-                              (const gauss::blur_item*)(dp + o_bitem), (const int2*)(dp + o_btab), (uint8_t*)(dp + o_bpix));
+    bw.launch_round<true>(ctx->stream, frames->dev, H, W, k, st, st.dev<uint8_t>(o_bpix));
   }
   TA_HIP(ctx, hipGetLastError());
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call

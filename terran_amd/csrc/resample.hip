@@ -22,16 +22,12 @@
 // pass then reads the frame or writes the result directly; when both are skipped the horizontal pass copies.
 // ta_frames_pixelate runs the same two kernels (BOX filter, the box as the cropped image) into small images in scratch
 // and pixelate_paste writes them back enlarged by NEAREST under the region's shape.
-#include "ta_internal.h"
-#include "region_rounds.h"
+#include "frame_regions.h"
 
 #include <math.h>
-#include <string.h>
+#include <stdio.h>
 
-#include <algorithm>
-#include <map>
 #include <tuple>
-#include <vector>
 
 namespace {
 
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(THREADS) void pixelate_paste(uint8_t* __restrict__ 
   const int x = (blockIdx.x % tiles_x) * TX + threadIdx.x % TX, y = blockIdx.y * TY + threadIdx.x / TX;
   if (x >= q.w || y >= q.h) return;
   if (q.span >= 0) {
-    const int2 sp = spans[q.span + y];
+    const int2 sp = spans[q.span + y];                  // clamped to the box (ta_span_tables); x is in 0 .. w - 1 anyway
     if (x < sp.x || x > sp.y) return;
   }
   const int sx = tab[q.xu + 2 * x], sy = tab[q.yu + 2 * y];
@@ -325,7 +321,9 @@ rs_rec make_rec(table_set& ts, int frame, int sx0, int sy0, int w, int h, float 
   return r;
 }
 
-struct staged {               // records, tables and span tables in the scratch, the pixels behind them
+// Records, tables and span tables of a call in the context's scratch, the pixels behind them: one H2D copy.  Both blocks
+// keep the 16 slack bytes they always had: it was not shown from the kernels that nothing reads past the staged tables.
+struct staged {
   const rs_rec* recs;
   const int32_t* tab;
   const int2* spans;
@@ -334,22 +332,11 @@ struct staged {               // records, tables and span tables in the scratch,
 
 int stage(ta_ctx* ctx, const std::vector<rs_rec>& recs, const std::vector<int32_t>& tab, const std::vector<int2>& spans,
           size_t pixel_bytes, staged* s) {
-  const size_t b_rec = recs.size() * sizeof(rs_rec), b_tab = tab.size() * sizeof(int32_t), b_span = spans.size() * sizeof(int2);
-  const size_t o_tab = (b_rec + 15) & ~(size_t)15, o_span = (o_tab + b_tab + 15) & ~(size_t)15;
-  const size_t bytes = o_span + b_span, o_pix = (bytes + 255) & ~(size_t)255;
-  void *scr = nullptr, *pin = nullptr;
-  TA_TRY(ta_scratch(ctx, o_pix + pixel_bytes + 16, &scr));
-  TA_TRY(ta_pinned(ctx, bytes + 16, &pin));
-  char* hp = (char*)pin;
-  memcpy(hp, recs.data(), b_rec);
-  if (b_tab) memcpy(hp + o_tab, tab.data(), b_tab);
-  if (b_span) memcpy(hp + o_span, spans.data(), b_span);
-  TA_HIP(ctx, hipMemcpyAsync(scr, pin, bytes, hipMemcpyHostToDevice, ctx->stream));
-  char* dp = (char*)scr;
-  s->recs = (const rs_rec*)dp;
-  s->tab = (const int32_t*)(dp + o_tab);
-  s->spans = (const int2*)(dp + o_span);
-  s->pixels = (uint8_t*)(dp + o_pix);
+  ta_staging st;
+  st.slack = 16;
+  const size_t o_rec = st.put(recs), o_tab = st.put(tab), o_span = st.put(spans), o_pix = st.device_only(pixel_bytes);
+  TA_TRY(st.commit(ctx));
+  *s = {st.dev<const rs_rec>(o_rec), st.dev<const int32_t>(o_tab), st.dev<const int2>(o_span), st.dev<uint8_t>(o_pix)};
   return TA_OK;
 }
 
@@ -394,8 +381,8 @@ extern "C" int ta_frames_resample(ta_ctx* ctx, const ta_frames* src, const ta_re
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
   if (out) *out = nullptr;
-  if (!src || !out || n < 0 || (n > 0 && !regions)) return ta_fail(ctx, TA_E_INVALID, "frames_resample: bad args");
-  if (src->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_resample: the batch lives on another device");
+  if (!out) return ta_fail(ctx, TA_E_INVALID, "frames_resample: bad args");
+  TA_TRY(ta_check_batch(ctx, "frames_resample", src, regions, n));
   double (*f)(double);
   double support;
   if (!filter_of(filter, &f, &support)) return ta_fail(ctx, TA_E_INVALID, "frames_resample: unknown filter %d", filter);
@@ -404,7 +391,7 @@ extern "C" int ta_frames_resample(ta_ctx* ctx, const ta_frames* src, const ta_re
   const int N = src->n, H = src->h, W = src->w;
   for (int i = 0; i < n; ++i) {
     const ta_resample_region& q = regions[i];
-    if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "frames_resample: region %d: frame %d out of range [0, %d)", i, q.frame, N);
+    TA_TRY(ta_check_frame(ctx, "frames_resample", i, q.frame, N));
     if (!box_ok(q.x0, q.x1, W) || !box_ok(q.y0, q.y1, H))
       return ta_fail(ctx, TA_E_INVALID, "frames_resample: region %d: box (%g, %g, %g, %g) must satisfy 0 <= x0 < x1 <= %d, 0 <= y0 < y1 <= %d", i,
                      q.x0, q.y0, q.x1, q.y1, W, H);
@@ -441,62 +428,44 @@ extern "C" int ta_frames_resample(ta_ctx* ctx, const ta_frames* src, const ta_re
 extern "C" int ta_frames_pixelate(ta_ctx* ctx, ta_frames* frames, const ta_pixelate_region* regions, int n) {
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
-  if (!frames || n < 0 || (n > 0 && !regions)) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: bad args");
-  if (frames->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: the batch lives on another device");
-  const int N = frames->n, H = frames->h, W = frames->w;
-  for (int i = 0; i < n; ++i) {
-    const ta_pixelate_region& q = regions[i];
-    if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: frame %d out of range [0, %d)", i, q.frame, N);
-    if (q.x1 <= q.x0 || q.y1 <= q.y0) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: empty or inverted box", i);
-    if (q.shape != TA_BLUR_BOX && q.shape != TA_BLUR_ELLIPSE) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: unknown shape", i);
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > W || q.y1 > H)
-      return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: [%d, %d) x [%d, %d) is not inside the %d x %d frame", i, q.x0, q.x1, q.y0, q.y1, W, H);
-    if (q.x1 - q.x0 > MAX_OUT || q.y1 - q.y0 > MAX_OUT)
-      return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: a side longer than %d", i, MAX_OUT);
-    if (q.block < 1 || q.block > MAX_OUT) return ta_fail(ctx, TA_E_INVALID, "frames_pixelate: region %d: block %d, must be 1 .. %d", i, q.block, MAX_OUT);
-  }
+  char why[64];
+  TA_TRY(ta_check_regions(ctx, "frames_pixelate", frames, regions, n, MAX_OUT, [&](const ta_pixelate_region& q) {
+    if (q.block >= 1 && q.block <= MAX_OUT) return (const char*)nullptr;
+    snprintf(why, sizeof(why), "block %d, must be 1 .. %d", q.block, MAX_OUT);
+    return (const char*)why;
+  }));
   if (n == 0) return TA_OK;
 
-  std::vector<int32_t> round;
-  const int rounds = ta_plan_rounds(regions, n, round);
+  const int H = frames->h, W = frames->w;
   table_set ts;
   std::vector<rs_rec> recs;
-  std::vector<int2> spans;
-  std::map<std::pair<int, int>, int> span_of;
-  std::vector<size_t> first(rounds + 1, 0);
-  size_t pixel_bytes = 0;
-  for (int k = 0; k < rounds; ++k) {
-    first[k] = recs.size();
-    size_t small_at = 0, mid_at = 0;
-    for (int i = 0; i < n; ++i) {
-      const ta_pixelate_region& q = regions[i];
-      if (round[i] != k || q.block == 1) continue;      // block 1: the region as it is
-      const int w = q.x1 - q.x0, h = q.y1 - q.y0, sw = std::max(1, w / q.block), sh = std::max(1, h / q.block);
-      rs_rec r = make_rec(ts, q.frame, q.x0, q.y0, w, h, 0.f, 0.f, (float)w, (float)h, sw, sh, TA_RESAMPLE_BOX, &mid_at);
-      r.w = w, r.h = h;
-      r.xu = ts.axis(sw, 0.f, (float)sw, w, TA_RESAMPLE_NEAREST).b;
-      r.yu = ts.axis(sh, 0.f, (float)sh, h, TA_RESAMPLE_NEAREST).b;
-      if (q.shape == TA_BLUR_ELLIPSE) {
-        auto it = span_of.find({w, h});
-        if (it == span_of.end()) {
-          it = span_of.emplace(std::make_pair(w, h), (int)spans.size()).first;
-          ta_disc_rows(w - 1, h - 1, spans);            // rows 0 .. h - 1 of ellipse([0, 0, w - 1, h - 1])
-        }
-        r.span = it->second;
-      }
-      r.out = small_at;
-      small_at += ((size_t)sw * sh * 3 + 15) & ~(size_t)15;
-      recs.push_back(r);
-    }
-    for (size_t j = first[k]; j < recs.size(); ++j) recs[j].mid += small_at;   // the round's small images, then its horizontal results
-    pixel_bytes = std::max(pixel_bytes, small_at + mid_at);
-  }
-  first[rounds] = recs.size();
+  ta_span_tables spans;
+  std::vector<size_t> first(1, 0);                      // the first record of every round, and the end
+  size_t pixel_bytes = 0, small_at = 0, mid_at = 0;
+  const int rounds = ta_each_round(
+      regions, n,
+      [&](const ta_pixelate_region& q) {
+        if (q.block == 1) return;                       // block 1: the region as it is
+        const int w = q.x1 - q.x0, h = q.y1 - q.y0, sw = std::max(1, w / q.block), sh = std::max(1, h / q.block);
+        rs_rec r = make_rec(ts, q.frame, q.x0, q.y0, w, h, 0.f, 0.f, (float)w, (float)h, sw, sh, TA_RESAMPLE_BOX, &mid_at);
+        r.w = w, r.h = h;
+        r.xu = ts.axis(sw, 0.f, (float)sw, w, TA_RESAMPLE_NEAREST).b;
+        r.yu = ts.axis(sh, 0.f, (float)sh, h, TA_RESAMPLE_NEAREST).b;
+        if (q.shape == TA_BLUR_ELLIPSE) r.span = spans.of(w, h);
+        r.out = small_at;
+        small_at += ((size_t)sw * sh * 3 + 15) & ~(size_t)15;
+        recs.push_back(r);
+      },
+      [&] {
+        for (size_t j = first.back(); j < recs.size(); ++j) recs[j].mid += small_at;   // the round's small images, then its horizontal results
+        pixel_bytes = std::max(pixel_bytes, small_at + mid_at);
+        first.push_back(recs.size());
+        small_at = mid_at = 0;
+      });
   if (recs.empty()) return TA_OK;
-  if (spans.empty()) spans.push_back(make_int2(1, 0));
 
   staged s;
-  TA_TRY(stage(ctx, recs, ts.tab, spans, pixel_bytes, &s));
+  TA_TRY(stage(ctx, recs, ts.tab, spans.table(), pixel_bytes, &s));
   for (int k = 0; k < rounds; ++k) {
     const size_t count = first[k + 1] - first[k];
     if (!count) continue;

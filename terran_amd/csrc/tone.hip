@@ -18,25 +18,22 @@
 // one 4), the workgroup sums its four copies and adds every non-zero bin to the region's bins in device memory with one
 // global integer atomic.  Integer sums do not depend on their order: the result is deterministic.  A flat frame sends
 // every lane of a wave to one LDS address, which the LDS serialises; the global atomics stay one per bin and workgroup.
-// The in-place kernels run in rounds of regions that are pairwise disjoint within their frame (region_rounds.h), one
+// The in-place kernels run in rounds of regions that are pairwise disjoint within their frame (frame_regions.h), one
 // launch per round.
 #include "ta_internal.h"
 #include "pixel_walk.h"
-#include "region_rounds.h"
+#include "frame_regions.h"
 
 #include <math.h>
 #include <string.h>
 
-#include <algorithm>
-#include <map>
 #include <utility>
 #include <vector>
 
 namespace {
 
-constexpr int THREADS = 256, WAVE = WALK_WAVE, WAVES = THREADS / WAVE;
+constexpr int THREADS = WALK_THREADS, WAVE = WALK_WAVE, WAVES = WALK_WAVES;
 constexpr int MAX_SIDE = 16384;            // of a region: 2^28 pixels at most, so a count fits uint32
-constexpr int STRIP_PIXELS = 16384;        // pixels of one workgroup's strip of rows (at least one row per wave)
 
 struct tone_rec {            // 32 bytes
   int32_t frame, x0, y0, w, h;
@@ -46,22 +43,7 @@ struct tone_rec {            // 32 bytes
 };
 static_assert(sizeof(tone_rec) == 32, "tone_rec");
 
-struct tone_item {           // one workgroup's strip: rows start .. start + count - 1 of the region
-  int32_t rec, start, count;
-};
-
 __device__ inline uint32_t luma(uint32_t r, uint32_t g, uint32_t b) { return (19595u * r + 38470u * g + 7471u * b + 0x8000u) >> 16; }
-
-// rows of the strip, wave by wave: body(first pixel of the row's span, pixels in it)
-template <class P, class F>
-__device__ inline void walk_strip(P* frames, int H, int W, const tone_rec& q, const tone_item& it, const int2* __restrict__ tabs, F body) {
-  const int wave = threadIdx.x / WAVE;
-  for (int r = it.start + wave; r < it.start + it.count; r += WAVES) {
-    const int2 span = q.tab >= 0 ? tabs[q.tab + r] : make_int2(0, q.w - 1);   // clamped to the box on the host
-    if (span.x > span.y) continue;
-    body(frames + (((size_t)q.frame * H + q.y0 + r) * (size_t)W + q.x0 + span.x) * 3, span.y - span.x + 1);
-  }
-}
 
 // the twelve bytes of a group: d[0] = R0 G0 B0 R1, d[1] = G1 B1 R2 G2, d[2] = B2 R3 G3 B3 (lowest byte first)
 struct quad {
@@ -90,17 +72,17 @@ __device__ inline void count4(uint32_t* bins, const uint32_t v[4]) {
 
 template <int MODE>
 __global__ __launch_bounds__(THREADS) void hist_kernel(const uint8_t* __restrict__ frames, int H, int W,
-                                                       const tone_rec* __restrict__ recs, const tone_item* __restrict__ items,
+                                                       const tone_rec* __restrict__ recs, const strip_item* __restrict__ items,
                                                        const int2* __restrict__ tabs, uint32_t* __restrict__ bins) {
   constexpr int NB = MODE == TA_HIST_RGB ? 768 : 256;
   __shared__ uint32_t lds[WAVES * NB];
   for (int i = threadIdx.x; i < WAVES * NB; i += THREADS) lds[i] = 0;
   __syncthreads();
-  const tone_item it = items[blockIdx.x];
+  const strip_item it = items[blockIdx.x];
   const tone_rec q = recs[it.rec];
   uint32_t* mine = lds + (threadIdx.x / WAVE) * NB;
   const int lane = threadIdx.x % WAVE;
-  walk_strip(frames, H, W, q, it, tabs, [&](const uint8_t* p, int npx) {
+  walk_strip(frames, H, W, q, it, tabs, [&](const uint8_t* p, int npx, int, int) {
     walk_row(
         p, npx, lane,
         [&](const uint8_t* px) {
@@ -136,16 +118,16 @@ __global__ __launch_bounds__(THREADS) void hist_kernel(const uint8_t* __restrict
 }
 
 __global__ __launch_bounds__(THREADS) void point_kernel(uint8_t* __restrict__ frames, int H, int W, const tone_rec* __restrict__ recs,
-                                                        const tone_item* __restrict__ items, const int2* __restrict__ tabs,
+                                                        const strip_item* __restrict__ items, const int2* __restrict__ tabs,
                                                         const uint8_t* __restrict__ luts) {
   __shared__ uint32_t words[192];
-  const tone_item it = items[blockIdx.x];
+  const strip_item it = items[blockIdx.x];
   const tone_rec q = recs[it.rec];
   const uint32_t* src = (const uint32_t*)(luts + (size_t)q.arg * 768);     // tables start on a 16-byte boundary, 768 apart
   if (threadIdx.x < 192) words[threadIdx.x] = src[threadIdx.x];
   __syncthreads();
   const uint8_t *tr = (const uint8_t*)words, *tg = tr + 256, *tb = tr + 512;
-  walk_strip(frames, H, W, q, it, tabs, [&](uint8_t* p, int npx) {
+  walk_strip(frames, H, W, q, it, tabs, [&](uint8_t* p, int npx, int, int) {
     walk_row(
         p, npx, threadIdx.x % WAVE,
         [&](uint8_t* px) {
@@ -163,12 +145,12 @@ __global__ __launch_bounds__(THREADS) void point_kernel(uint8_t* __restrict__ fr
 }
 
 __global__ __launch_bounds__(THREADS) void saturate_kernel(uint8_t* __restrict__ frames, int H, int W, const tone_rec* __restrict__ recs,
-                                                           const tone_item* __restrict__ items, const int2* __restrict__ tabs) {
-  const tone_item it = items[blockIdx.x];
+                                                           const strip_item* __restrict__ items, const int2* __restrict__ tabs) {
+  const strip_item it = items[blockIdx.x];
   const tone_rec q = recs[it.rec];
   const float f = q.factor;
   const bool inside = f >= 0.f && f <= 1.f;
-  walk_strip(frames, H, W, q, it, tabs, [&](uint8_t* p, int npx) {
+  walk_strip(frames, H, W, q, it, tabs, [&](uint8_t* p, int npx, int, int) {
     walk_row(
         p, npx, threadIdx.x % WAVE,
         [&](uint8_t* px) {
@@ -192,105 +174,47 @@ __global__ __launch_bounds__(THREADS) void saturate_kernel(uint8_t* __restrict__
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------
-// the checks the three calls share; `extra(region)`: a call's own defect, or nullptr
-template <class R, class F>
-int check_regions(ta_ctx* ctx, const char* who, const ta_frames* frames, const R* regions, int n, F extra) {
-  if (!frames || n < 0 || (n > 0 && !regions)) return ta_fail(ctx, TA_E_INVALID, "%s: bad args", who);
-  if (frames->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "%s: the batch lives on another device", who);
-  const int N = frames->n, H = frames->h, W = frames->w;
-  for (int i = 0; i < n; ++i) {
-    const R& q = regions[i];
-    if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "%s: region %d: frame %d out of range [0, %d)", who, i, q.frame, N);
-    if (q.x1 <= q.x0 || q.y1 <= q.y0) return ta_fail(ctx, TA_E_INVALID, "%s: region %d: empty or inverted box", who, i);
-    if (q.shape != TA_BLUR_BOX && q.shape != TA_BLUR_ELLIPSE) return ta_fail(ctx, TA_E_INVALID, "%s: region %d: unknown shape", who, i);
-    if (q.x0 < 0 || q.y0 < 0 || q.x1 > W || q.y1 > H)
-      return ta_fail(ctx, TA_E_INVALID, "%s: region %d: [%d, %d) x [%d, %d) is not inside the %d x %d frame", who, i, q.x0, q.x1, q.y0, q.y1, W, H);
-    if (q.x1 - q.x0 > MAX_SIDE || q.y1 - q.y0 > MAX_SIDE)
-      return ta_fail(ctx, TA_E_INVALID, "%s: region %d: a side longer than %d", who, i, MAX_SIDE);
-    if (const char* why = extra(q)) return ta_fail(ctx, TA_E_INVALID, "%s: region %d: %s", who, i, why);
-  }
-  return TA_OK;
-}
-
 // What one call launches: a record per region that does something, round by round, the strips of every round (one
-// workgroup each) and the ellipse span tables, every span clamped to its box.
+// workgroup each) and the ellipse span tables; checks, rounds, span tables and staging are frame_regions.h's.
 struct tone_work {
   std::vector<tone_rec> recs;
-  std::vector<tone_item> items;
-  std::vector<int2> tab;
+  std::vector<strip_item> items;
+  ta_span_tables spans;
   std::vector<std::pair<int, int>> launches;   // first strip and strips of every round
-  std::map<std::pair<int, int>, int> tab_of;
+  size_t closed = 0;                           // records of the rounds closed so far
 
   template <class R>
   tone_rec& add(const R& q) {
     tone_rec r;
     memset(&r, 0, sizeof(r));
     r.frame = q.frame, r.x0 = q.x0, r.y0 = q.y0, r.w = q.x1 - q.x0, r.h = q.y1 - q.y0;
-    r.tab = -1;
-    if (q.shape == TA_BLUR_ELLIPSE) {
-      auto it = tab_of.find({r.w, r.h});
-      if (it == tab_of.end()) {
-        const size_t first = tab.size();
-        it = tab_of.emplace(std::make_pair(r.w, r.h), (int)first).first;
-        ta_disc_rows(r.w - 1, r.h - 1, tab);                // rows 0 .. h - 1 of ellipse([0, 0, w - 1, h - 1])
-        tab.resize(first + r.h, make_int2(1, 0));
-        for (size_t k = first; k < tab.size(); ++k) tab[k] = make_int2(std::max(tab[k].x, 0), std::min(tab[k].y, r.w - 1));
-      }
-      r.tab = it->second;
-    }
+    r.tab = q.shape == TA_BLUR_ELLIPSE ? spans.of(r.w, r.h) : -1;
     recs.push_back(r);
     return recs.back();
   }
-  // closes a round: the strips of the records from `first` on
-  void strips(size_t first) {
+  // closes a round: the strips of the records added since the last one
+  void close() {
     const int at = (int)items.size();
-    for (size_t j = first; j < recs.size(); ++j) {
-      const int rows = std::max(WAVES, STRIP_PIXELS / recs[j].w);
-      for (int y = 0; y < recs[j].h; y += rows) items.push_back({(int32_t)j, y, std::min(rows, recs[j].h - y)});
-    }
-    launches.push_back({at, (int)items.size() - at});
+    launches.push_back({at, ta_add_strips(items, recs, closed, WALK_WAVES, STRIP_PIXELS)});
+    closed = recs.size();
   }
+  // records, strips and span tables into the call's staging; after its commit, where they are on the device
+  size_t o_rec = 0, o_item = 0, o_tab = 0;
+  void put(ta_staging& st) { o_rec = st.put(recs), o_item = st.put(items), o_tab = st.put(spans.table()); }
+  const tone_rec* d_recs(const ta_staging& st) const { return st.dev<const tone_rec>(o_rec); }
+  const strip_item* d_items(const ta_staging& st) const { return st.dev<const strip_item>(o_item); }
+  const int2* d_tab(const ta_staging& st) const { return st.dev<const int2>(o_tab); }
 };
-
-// records, strips, tables and `extra` bytes behind them (16-byte aligned) into the context's scratch; `more` further
-// device bytes behind those (256-byte aligned, not copied)
-struct tone_staged {
-  const tone_rec* recs;
-  const tone_item* items;
-  const int2* tab;
-  char *extra, *more;
-};
-int stage(ta_ctx* ctx, tone_work& w, const void* extra, size_t b_extra, size_t more, size_t pinned_more, tone_staged* out, char** pin_more) {
-  if (w.tab.empty()) w.tab.push_back(make_int2(1, 0));
-  const size_t b_rec = w.recs.size() * sizeof(tone_rec), b_item = w.items.size() * sizeof(tone_item), b_tab = w.tab.size() * sizeof(int2);
-  const size_t o_item = (b_rec + 15) & ~(size_t)15, o_tab = (o_item + b_item + 15) & ~(size_t)15;
-  const size_t o_extra = (o_tab + b_tab + 15) & ~(size_t)15, staged = o_extra + b_extra, o_more = (staged + 255) & ~(size_t)255;
-  void *scr = nullptr, *pin = nullptr;
-  TA_TRY(ta_scratch(ctx, o_more + more, &scr));
-  TA_TRY(ta_pinned(ctx, o_more + pinned_more, &pin));
-  char* hp = (char*)pin;
-  memcpy(hp, w.recs.data(), b_rec);
-  memcpy(hp + o_item, w.items.data(), b_item);
-  memcpy(hp + o_tab, w.tab.data(), b_tab);
-  if (b_extra) memcpy(hp + o_extra, extra, b_extra);
-  TA_HIP(ctx, hipMemcpyAsync(scr, pin, staged, hipMemcpyHostToDevice, ctx->stream));
-  char* dp = (char*)scr;
-  *out = {(const tone_rec*)dp, (const tone_item*)(dp + o_item), (const int2*)(dp + o_tab), dp + o_extra, dp + o_more};
-  if (pin_more) *pin_more = hp + o_more;
-  return TA_OK;
-}
 
 // the records of an in-place call, round by round; skip(region): the region changes nothing
 template <class R, class S, class F>
 void plan_rounds(const R* regions, int n, tone_work& w, S skip, F fill) {
-  std::vector<int32_t> round;
-  const int rounds = ta_plan_rounds(regions, n, round);
-  for (int k = 0; k < rounds; ++k) {
-    const size_t first = w.recs.size();
-    for (int i = 0; i < n; ++i)
-      if (round[i] == k && !skip(regions[i])) fill(w.add(regions[i]), regions[i]);
-    w.strips(first);
-  }
+  ta_each_round(
+      regions, n,
+      [&](const R& q) {
+        if (!skip(q)) fill(w.add(q), q);
+      },
+      [&] { w.close(); });
 }
 
 }  // namespace
@@ -298,30 +222,32 @@ void plan_rounds(const R* regions, int n, tone_work& w, S skip, F fill) {
 extern "C" int ta_frames_histogram(ta_ctx* ctx, const ta_frames* frames, const ta_hist_region* regions, int n, int mode, uint32_t* hist) {
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
-  TA_TRY(check_regions(ctx, "frames_histogram", frames, regions, n, [](const ta_hist_region&) { return (const char*)nullptr; }));
+  TA_TRY(ta_check_regions(ctx, "frames_histogram", frames, regions, n, MAX_SIDE, [](const ta_hist_region&) { return (const char*)nullptr; }));
   if (mode != TA_HIST_RGB && mode != TA_HIST_L) return ta_fail(ctx, TA_E_INVALID, "frames_histogram: unknown mode %d", mode);
   if (n == 0) return TA_OK;
   if (!hist) return ta_fail(ctx, TA_E_INVALID, "frames_histogram: hist is NULL");
 
   tone_work w;
   for (int i = 0; i < n; ++i) w.add(regions[i]).arg = i;
-  w.strips(0);
+  w.close();
   const size_t b_bins = (size_t)n * (mode == TA_HIST_RGB ? 768 : 256) * sizeof(uint32_t);
-  tone_staged s;
-  char* host_bins = nullptr;
-  TA_TRY(stage(ctx, w, nullptr, 0, b_bins, b_bins, &s, &host_bins));
-  TA_HIP(ctx, hipMemsetAsync(s.more, 0, b_bins, ctx->stream));
+  ta_staging st;                                    // one H2D copy; the bins behind it on the device, and pinned for the read-back
+  w.put(st);
+  const size_t o_bins = st.device_only(b_bins), o_host = st.host_only(b_bins);
+  TA_TRY(st.commit(ctx));
+  uint32_t* bins = st.dev<uint32_t>(o_bins);
+  TA_HIP(ctx, hipMemsetAsync(bins, 0, b_bins, ctx->stream));
   const int strips = w.launches[0].second;
   if (mode == TA_HIST_RGB)
     hipLaunchKernelGGL(hist_kernel<TA_HIST_RGB>, dim3(strips), dim3(THREADS), 0, ctx->stream, (const uint8_t*)frames->dev, frames->h,
-                       frames->w, s.recs, s.items, s.tab, (uint32_t*)s.more);
+                       frames->w, w.d_recs(st), w.d_items(st), w.d_tab(st), bins);
   else
     hipLaunchKernelGGL(hist_kernel<TA_HIST_L>, dim3(strips), dim3(THREADS), 0, ctx->stream, (const uint8_t*)frames->dev, frames->h,
-                       frames->w, s.recs, s.items, s.tab, (uint32_t*)s.more);
+                       frames->w, w.d_recs(st), w.d_items(st), w.d_tab(st), bins);
   TA_HIP(ctx, hipGetLastError());
-  TA_HIP(ctx, hipMemcpyAsync(host_bins, s.more, b_bins, hipMemcpyDeviceToHost, ctx->stream));
+  TA_HIP(ctx, hipMemcpyAsync(st.host<uint32_t>(o_host), bins, b_bins, hipMemcpyDeviceToHost, ctx->stream));
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call
-  memcpy(hist, host_bins, b_bins);
+  memcpy(hist, st.host<uint32_t>(o_host), b_bins);
   return TA_OK;
 }
 
@@ -329,18 +255,20 @@ extern "C" int ta_frames_point(ta_ctx* ctx, ta_frames* frames, const ta_point_re
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
   if (n_luts < 0 || (n > 0 && !luts)) return ta_fail(ctx, TA_E_INVALID, "frames_point: bad args");
-  TA_TRY(check_regions(ctx, "frames_point", frames, regions, n,
-                       [&](const ta_point_region& q) { return q.lut < 0 || q.lut >= n_luts ? "lut index out of range" : (const char*)nullptr; }));
+  TA_TRY(ta_check_regions(ctx, "frames_point", frames, regions, n, MAX_SIDE,
+                          [&](const ta_point_region& q) { return q.lut < 0 || q.lut >= n_luts ? "lut index out of range" : (const char*)nullptr; }));
   if (n == 0) return TA_OK;
 
   tone_work w;
   plan_rounds(regions, n, w, [](const ta_point_region&) { return false; }, [](tone_rec& r, const ta_point_region& q) { r.arg = q.lut; });
-  tone_staged s;
-  TA_TRY(stage(ctx, w, luts, (size_t)n_luts * 768, 0, 0, &s, nullptr));
+  ta_staging st;                                    // one H2D copy
+  w.put(st);
+  const size_t o_luts = st.put(luts, (size_t)n_luts * 768, 16);   // point_kernel reads the tables as dwords: a 16-byte boundary
+  TA_TRY(st.commit(ctx));
   for (const auto& L : w.launches)
     if (L.second)
-      hipLaunchKernelGGL(point_kernel, dim3(L.second), dim3(THREADS), 0, ctx->stream, frames->dev, frames->h, frames->w, s.recs,
-                         s.items + L.first, s.tab, (const uint8_t*)s.extra);
+      hipLaunchKernelGGL(point_kernel, dim3(L.second), dim3(THREADS), 0, ctx->stream, frames->dev, frames->h, frames->w, w.d_recs(st),
+                         w.d_items(st) + L.first, w.d_tab(st), st.dev<const uint8_t>(o_luts));
   TA_HIP(ctx, hipGetLastError());
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call
   return TA_OK;
@@ -349,20 +277,21 @@ extern "C" int ta_frames_point(ta_ctx* ctx, ta_frames* frames, const ta_point_re
 extern "C" int ta_frames_saturate(ta_ctx* ctx, ta_frames* frames, const ta_saturate_region* regions, int n) {
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
-  TA_TRY(check_regions(ctx, "frames_saturate", frames, regions, n,
-                       [](const ta_saturate_region& q) { return isfinite(q.factor) ? (const char*)nullptr : "factor not finite"; }));
+  TA_TRY(ta_check_regions(ctx, "frames_saturate", frames, regions, n, MAX_SIDE,
+                          [](const ta_saturate_region& q) { return isfinite(q.factor) ? (const char*)nullptr : "factor not finite"; }));
   if (n == 0) return TA_OK;
 
   tone_work w;
   plan_rounds(regions, n, w, [](const ta_saturate_region& q) { return q.factor == 1.f; },    // Image.blend copies the image
               [](tone_rec& r, const ta_saturate_region& q) { r.factor = q.factor; });
   if (w.recs.empty()) return TA_OK;
-  tone_staged s;
-  TA_TRY(stage(ctx, w, nullptr, 0, 0, 0, &s, nullptr));
+  ta_staging st;                                    // one H2D copy
+  w.put(st);
+  TA_TRY(st.commit(ctx));
   for (const auto& L : w.launches)
     if (L.second)
-      hipLaunchKernelGGL(saturate_kernel, dim3(L.second), dim3(THREADS), 0, ctx->stream, frames->dev, frames->h, frames->w, s.recs,
-                         s.items + L.first, s.tab);
+      hipLaunchKernelGGL(saturate_kernel, dim3(L.second), dim3(THREADS), 0, ctx->stream, frames->dev, frames->h, frames->w, w.d_recs(st),
+                         w.d_items(st) + L.first, w.d_tab(st));
   TA_HIP(ctx, hipGetLastError());
   TA_HIP(ctx, hipStreamSynchronize(ctx->stream));   // pinned / scratch staging is reused by the next call
   return TA_OK;

@@ -23,14 +23,11 @@
 // image), byte by byte otherwise and for the ragged tail at the image's end.  The source is gathered with byte loads.
 // transpose_kernel: a 32 x 32 pixel tile goes through LDS (one dword per pixel, rows padded to 33) so that, for the four
 // ops that swap the axes, consecutive lanes read consecutive source pixels AND write consecutive output pixels.
-#include "ta_internal.h"
+#include "frame_regions.h"
 
 #include <math.h>
-#include <string.h>
 
-#include <map>
 #include <tuple>
-#include <vector>
 
 namespace {
 
@@ -257,8 +254,8 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
   ta_enter(ctx);
   if (!ctx) return TA_E_INVALID;
   if (out) *out = nullptr;
-  if (!src || !out || n < 0 || (n > 0 && !regions)) return ta_fail(ctx, TA_E_INVALID, "frames_transform: bad args");
-  if (src->ctx->device != ctx->device) return ta_fail(ctx, TA_E_INVALID, "frames_transform: the batch lives on another device");
+  if (!out) return ta_fail(ctx, TA_E_INVALID, "frames_transform: bad args");
+  TA_TRY(ta_check_batch(ctx, "frames_transform", src, regions, n));
   if (filter != TA_RESAMPLE_NEAREST && filter != TA_RESAMPLE_BILINEAR && filter != TA_RESAMPLE_BICUBIC)
     return ta_fail(ctx, TA_E_INVALID, "frames_transform: filter %d, must be NEAREST, BILINEAR or BICUBIC", filter);
   if (out_h <= 0 || out_w <= 0 || out_h > MAX_OUT || out_w > MAX_OUT)
@@ -266,7 +263,7 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
   const int N = src->n, H = src->h, W = src->w;
   for (int i = 0; i < n; ++i) {
     const ta_transform_region& q = regions[i];
-    if (q.frame < 0 || q.frame >= N) return ta_fail(ctx, TA_E_INVALID, "frames_transform: region %d: frame %d out of range [0, %d)", i, q.frame, N);
+    TA_TRY(ta_check_frame(ctx, "frames_transform", i, q.frame, N));
     if (q.method != TA_TRANSFORM_AFFINE && q.method != TA_TRANSFORM_PERSPECTIVE)
       return ta_fail(ctx, TA_E_INVALID, "frames_transform: region %d: unknown method %d", i, q.method);
     for (int k = 0; k < (q.method == TA_TRANSFORM_AFFINE ? 6 : 8); ++k)
@@ -279,7 +276,7 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
     return ta_fail(ctx, TA_E_INVALID, "frames_transform: %d regions of %d x %d are more than one launch holds", n, out_w, out_h);
 
   std::vector<tf_rec> recs(n);
-  scale_tabs st;
+  scale_tabs st_tabs;
   bool accum = false;
   for (int i = 0; i < n; ++i) {
     const ta_transform_region& q = regions[i];
@@ -293,8 +290,8 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
       r.route = ROUTE_GENERIC;
     } else if (a[1] == 0 && a[3] == 0) {
       r.route = ROUTE_SCALE;
-      r.xtab = st.axis(a[2] + a[0] * 0.5, a[0], out_w, W);
-      r.ytab = st.axis(a[5] + a[4] * 0.5, a[4], out_h, H);
+      r.xtab = st_tabs.axis(a[2] + a[0] * 0.5, a[0], out_w, W);
+      r.ytab = st_tabs.axis(a[5] + a[4] * 0.5, a[4], out_h, H);
     } else if (check_fixed(a, 0, 0) && check_fixed(a, out_w, out_h) && check_fixed(a, 0, out_h) && check_fixed(a, out_w, 0)) {
       r.route = ROUTE_FIXED;
       r.f[0] = fix16(a[0]), r.f[1] = fix16(a[1]), r.f[3] = fix16(a[3]), r.f[4] = fix16(a[4]);
@@ -308,31 +305,25 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
 
   ta_frames* dst = nullptr;
   TA_TRY(ta_frames_alloc_uninit(ctx, n, out_h, out_w, &dst));
-  const size_t b_rec = recs.size() * sizeof(tf_rec), b_tab = st.tab.size() * sizeof(int32_t);
-  const size_t o_tab = (b_rec + 15) & ~(size_t)15, bytes = o_tab + b_tab;
-  void *scr = nullptr, *pin = nullptr;
-  int rc = ta_scratch(ctx, bytes + 16, &scr);
-  if (rc == TA_OK) rc = ta_pinned(ctx, bytes + 16, &pin);
+  ta_staging st;                                    // one H2D copy: records, then the scale tables
+  st.slack = 16;                                    // kept: not shown from the kernels that nothing reads past the tables
+  const size_t o_rec = st.put(recs), o_tab = st.put(st_tabs.tab);
+  int rc = st.commit(ctx);                          // a code, no return: dst is freed below on every failure
   if (rc == TA_OK) {
-    memcpy(pin, recs.data(), b_rec);
-    if (b_tab) memcpy((char*)pin + o_tab, st.tab.data(), b_tab);
-    hipError_t e = hipMemcpyAsync(scr, pin, bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) {
-      const tf_rec* drec = (const tf_rec*)scr;
-      const int32_t* dtab = (const int32_t*)((char*)scr + o_tab);
-      const dim3 grid((unsigned)(n * groups)), block(THREADS);
-      const uint8_t* in = src->dev;
-      if (filter == TA_RESAMPLE_NEAREST)
-        hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_NEAREST>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
-      else if (filter == TA_RESAMPLE_BILINEAR)
-        hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_BILINEAR>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
-      else
-        hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_BICUBIC>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
-      if (accum)
-        hipLaunchKernelGGL(transform_accum_rows, dim3((unsigned)(((int64_t)n * out_h + THREADS - 1) / THREADS)), block, 0, ctx->stream, in, H, W, drec,
-                           n, dst->dev, out_h, out_w, fill);
-      e = hipGetLastError();
-    }
+    const tf_rec* drec = st.dev<const tf_rec>(o_rec);
+    const int32_t* dtab = st.dev<const int32_t>(o_tab);
+    const dim3 grid((unsigned)(n * groups)), block(THREADS);
+    const uint8_t* in = src->dev;
+    if (filter == TA_RESAMPLE_NEAREST)
+      hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_NEAREST>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
+    else if (filter == TA_RESAMPLE_BILINEAR)
+      hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_BILINEAR>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
+    else
+      hipLaunchKernelGGL(transform_kernel<TA_RESAMPLE_BICUBIC>, grid, block, 0, ctx->stream, in, H, W, drec, dtab, dst->dev, out_h, out_w, groups, fill);
+    if (accum)
+      hipLaunchKernelGGL(transform_accum_rows, dim3((unsigned)(((int64_t)n * out_h + THREADS - 1) / THREADS)), block, 0, ctx->stream, in, H, W, drec,
+                         n, dst->dev, out_h, out_w, fill);
+    hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);             // pinned / scratch staging is reused by the next call
     if (e != hipSuccess) rc = ta_fail(ctx, TA_E_DEVICE, "frames_transform: %s", hipGetErrorString(e));
   }

@@ -200,19 +200,10 @@ def resize_frames(frames, size, resample='bicubic', box=None, ctx=None):
     'bilinear', 'hamming', 'bicubic', 'lanczos' or Pillow's integer code; `box`: Pillow's (x0, y0, x1, y1) source
     rectangle, fractional, applied to every frame (None: the whole frame).  `ctx`: the context the work runs on and the
     result belongs to (default: the first batch's own).  Every argument is checked before anything is launched."""
-    if isinstance(frames, lib.Frames):
-        batches = [frames]
-    elif isinstance(frames, (list, tuple)) and frames and all(isinstance(b, lib.Frames) for b in frames):
-        batches = list(frames)
-    else:
-        raise ValueError('resize_frames: a lib.Frames batch or a non-empty list of them')
+    who = 'resize_frames'
+    batches, _ = _batches(frames, who)
     code = lib.resample_filter(resample)
-    try:
-        width, height = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError('resize_frames: size must be (width, height), got %r' % (size,)) from None
-    if not (1 <= width <= lib.RESAMPLE_SIDE_LIMIT and 1 <= height <= lib.RESAMPLE_SIDE_LIMIT):
-        raise ValueError('resize_frames: size must be within 1 .. %d a side, got %r' % (lib.RESAMPLE_SIDE_LIMIT, size))
+    width, height = _size(size, who)
     if box is not None:
         box = tuple(float(np.float32(v)) for v in box)          # Pillow reads the box as float32
         if len(box) != 4:

@@ -124,10 +124,9 @@ def blur_plan(regions):
     """Host only (no context, no device): ta_blur_plan -> (round of every region, float32 box radius, uint32 (n, 2)
     weights ww, fw): what ta_frames_blur derives from a BLUR_DT array before it launches anything."""
     lib = load()
-    regions = np.ascontiguousarray(regions, dtype=BLUR_DT)
-    n = len(regions)
+    regions, p, n = _records(regions, BLUR_DT)
     rounds, fr, w = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 2), np.uint32)
-    rc = lib.ta_blur_plan(ptr(regions) if n else None, n, ptr(rounds), ptr(fr), ptr(w))
+    rc = lib.ta_blur_plan(p, n, ptr(rounds), ptr(fr), ptr(w))
     if rc != OK:
         raise TerranAmdError(rc, 'blur_plan: an empty or inverted box, an unknown shape or a bad radius')
     return rounds, fr, w
@@ -172,11 +171,11 @@ def filter_plan(regions, specs):
     kernels kernel / scale, float32 (n_specs,) offsets offset + 0.5): what ta_frames_filter derives from a FILTER_REGION_DT
     and a FILTER_SPEC_DT array before it launches anything; zeros for the specs that are no kernels."""
     lib = load()
-    regions = np.ascontiguousarray(regions, dtype=FILTER_REGION_DT)
+    regions, p, n = _records(regions, FILTER_REGION_DT)
     specs = np.ascontiguousarray(specs, dtype=FILTER_SPEC_DT).reshape(-1)
-    n, m = len(regions), len(specs)
+    m = len(specs)
     rounds, kernels, offsets = np.zeros(n, np.int32), np.zeros((m, 25), np.float32), np.zeros(m, np.float32)
-    rc = lib.ta_filter_plan(ptr(regions) if n else None, n, ptr(specs) if m else None, m, ptr(rounds), ptr(kernels), ptr(offsets))
+    rc = lib.ta_filter_plan(p, n, ptr(specs) if m else None, m, ptr(rounds), ptr(kernels), ptr(offsets))
     if rc != OK:
         raise TerranAmdError(rc, 'filter_plan: a bad box, shape or spec index, or a spec ta_frames_filter refuses')
     return rounds, kernels, offsets
@@ -373,6 +372,12 @@ def load():
 
 def ptr(a):
     return a.ctypes.data_as(c_void_p) if a is not None else None
+
+
+def _records(a, dtype):
+    """A record list as an ABI call takes it: (the contiguous array, its pointer or None when empty, its length)."""
+    a = np.ascontiguousarray(a, dtype=dtype)
+    return a, (ptr(a) if len(a) else None), len(a)
 
 
 class Context:
@@ -616,20 +621,19 @@ class Frames:
         (ta_frames_draw_masks); without it a DRAW_MASK primitive is an unknown kind.  `ctx`: the context the drawing runs
         on -- the CALLER's, as in `resize`."""
         ctx = ctx or self.ctx
-        prims = np.ascontiguousarray(prims, dtype=PRIM_DT)
-        pp = ptr(prims) if len(prims) else None
+        prims, pp, n = _records(prims, PRIM_DT)
         if masks is None:
-            ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, pp, len(prims)))
+            ctx.check(ctx.lib.ta_frames_draw(ctx.h, self.h, pp, n))
             return
         masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
-        ctx.check(ctx.lib.ta_frames_draw_masks(ctx.h, self.h, pp, len(prims), ptr(masks) if len(masks) else None, len(masks)))
+        ctx.check(ctx.lib.ta_frames_draw_masks(ctx.h, self.h, pp, n, ptr(masks) if len(masks) else None, len(masks)))
 
     def blur(self, regions, ctx=None):
         """Blur `regions` (a BLUR_DT array, in order) of this batch in place (ta_frames_blur): Pillow's GaussianBlur of each
         half-open box, pasted back under its shape.  `ctx`: the context the blur runs on -- the CALLER's, as in `draw`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=BLUR_DT)
-        ctx.check(ctx.lib.ta_frames_blur(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+        regions, p, n = _records(regions, BLUR_DT)
+        ctx.check(ctx.lib.ta_frames_blur(ctx.h, self.h, p, n))
 
     def resample(self, regions, out_h, out_w, filter, ctx=None):
         """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's resize((out_w, out_h), filter, box=) of the
@@ -637,10 +641,9 @@ class Frames:
         `filter`: a TA_RESAMPLE_* / Pillow code.  `ctx`: the context the work runs on and the result belongs to -- the
         CALLER's, as in `resize`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=RESAMPLE_DT)
+        regions, p, n = _records(regions, RESAMPLE_DT)
         hd = c_void_p()
-        ctx.check(ctx.lib.ta_frames_resample(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), int(out_h),
-                                             int(out_w), int(filter), C.byref(hd)))
+        ctx.check(ctx.lib.ta_frames_resample(ctx.h, self.h, p, n, int(out_h), int(out_w), int(filter), C.byref(hd)))
         return Frames(ctx, handle=hd) if hd.value else None
 
     def pixelate(self, regions, ctx=None):
@@ -648,18 +651,17 @@ class Frames:
         shrunk by its `block` with Pillow's BOX filter and enlarged again with NEAREST, pasted back under its shape.
         `ctx`: the context the work runs on -- the CALLER's, as in `draw`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=PIXELATE_DT)
-        ctx.check(ctx.lib.ta_frames_pixelate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+        regions, p, n = _records(regions, PIXELATE_DT)
+        ctx.check(ctx.lib.ta_frames_pixelate(ctx.h, self.h, p, n))
 
     def histogram(self, regions, mode=HIST_RGB, ctx=None):
         """uint32 (len(regions), 3, 256) (HIST_RGB) or (len(regions), 256) (HIST_L): Pillow's histogram of each region of a
         HIST_DT array under its shape (ta_frames_histogram).  The batch is only read.  `ctx`: the CALLER's, as in `blur`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=HIST_DT)
+        regions, p, n = _records(regions, HIST_DT)
         mode = int(mode)
-        hist = np.zeros((len(regions), 3, 256) if mode == HIST_RGB else (len(regions), 256), np.uint32)
-        ctx.check(ctx.lib.ta_frames_histogram(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), mode,
-                                              ptr(hist) if len(regions) else None))
+        hist = np.zeros((n, 3, 256) if mode == HIST_RGB else (n, 256), np.uint32)
+        ctx.check(ctx.lib.ta_frames_histogram(ctx.h, self.h, p, n, mode, ptr(hist) if n else None))
         return hist
 
     def point(self, regions, luts, ctx=None):
@@ -667,19 +669,18 @@ class Frames:
         point() of each half-open box, pasted back under its shape.  `luts`: uint8 (n_luts, 768), R, G and B table of each;
         a region's `lut` names its table."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=POINT_DT)
+        regions, p, n = _records(regions, POINT_DT)
         luts = np.ascontiguousarray(luts, dtype=np.uint8)
         if luts.ndim != 2 or luts.shape[1] != 768:
             raise ValueError('point: luts must be uint8 (n_luts, 768), got %s' % (luts.shape,))
-        ctx.check(ctx.lib.ta_frames_point(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions),
-                                          ptr(luts) if len(luts) else None, len(luts)))
+        ctx.check(ctx.lib.ta_frames_point(ctx.h, self.h, p, n, ptr(luts) if len(luts) else None, len(luts)))
 
     def saturate(self, regions, ctx=None):
         """Blend `regions` (a SATURATE_DT array, in order) of this batch with their own luma in place (ta_frames_saturate):
         Pillow's ImageEnhance.Color(region).enhance(factor), pasted back under its shape."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=SATURATE_DT)
-        ctx.check(ctx.lib.ta_frames_saturate(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions)))
+        regions, p, n = _records(regions, SATURATE_DT)
+        ctx.check(ctx.lib.ta_frames_saturate(ctx.h, self.h, p, n))
 
     def filter(self, regions, specs, ctx=None):
         """Filter `regions` (a FILTER_REGION_DT array, in order) of this batch in place (ta_frames_filter): Pillow's
@@ -687,10 +688,9 @@ class Frames:
         FILTER_SPEC_DT array: a convolution kernel, a rank filter or an unsharp mask; terran_amd.image.filter_spec makes
         one from a Pillow filter).  `ctx`: the CALLER's, as in `blur`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=FILTER_REGION_DT)
+        regions, p, n = _records(regions, FILTER_REGION_DT)
         specs = np.ascontiguousarray(specs, dtype=FILTER_SPEC_DT).reshape(-1)
-        ctx.check(ctx.lib.ta_frames_filter(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions),
-                                           ptr(specs) if len(specs) else None, len(specs)))
+        ctx.check(ctx.lib.ta_frames_filter(ctx.h, self.h, p, n, ptr(specs) if len(specs) else None, len(specs)))
 
     def transform(self, regions, out_h, out_w, filter, fill=None, ctx=None):
         """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), method, a,
@@ -698,11 +698,10 @@ class Frames:
         without regions.  `filter`: NEAREST, BILINEAR or BICUBIC; `fill`: None (zeros) or 3 values 0 .. 255.  `ctx`: the
         context the work runs on and the result belongs to -- the CALLER's, as in `resize`."""
         ctx = ctx or self.ctx
-        regions = np.ascontiguousarray(regions, dtype=TRANSFORM_DT)
+        regions, p, n = _records(regions, TRANSFORM_DT)
         rgb = None if fill is None else np.array(fill, np.uint8).reshape(3)
         hd = c_void_p()
-        ctx.check(ctx.lib.ta_frames_transform(ctx.h, self.h, ptr(regions) if len(regions) else None, len(regions), int(out_h),
-                                              int(out_w), int(filter), ptr(rgb), C.byref(hd)))
+        ctx.check(ctx.lib.ta_frames_transform(ctx.h, self.h, p, n, int(out_h), int(out_w), int(filter), ptr(rgb), C.byref(hd)))
         return Frames(ctx, handle=hd) if hd.value else None
 
     def transpose(self, op, ctx=None):
