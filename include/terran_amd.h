@@ -367,6 +367,73 @@ int ta_frames_filter(ta_ctx* ctx, ta_frames* frames, const ta_filter_region* reg
 int ta_filter_plan(const ta_filter_region* regions, int n, const ta_filter_spec* specs, int n_specs, int32_t* rounds,
                    float* kernels, float* offsets);
 
+/* ---- combining two batches: paste, blend, ImageChops ---------------------------------------- */
+/* Pillow's operations of two images on regions of `dst`, in place and bit for bit.  Per region, with a = dst.crop(box) and
+ * b = src.crop(the equally sized box at (src_x, src_y) of frame src_frame), the call does dst.paste(R, box) -- under
+ * TA_BLUR_ELLIPSE only the ellipse's pixels change -- where R is
+ *     TA_COMBINE_PASTE   a with b pasted under the region's mask: a.paste(b, (0, 0), mask), and so Image.composite
+ *     TA_COMBINE_BLEND   Image.blend(a, b, alpha): the unfused float32 expression of ta_frames_saturate
+ *     the others         ImageChops.lighter / darker / difference / multiply / screen / add(a, b, scale = alpha, offset) /
+ *                        subtract(likewise) / add_modulo / subtract_modulo / soft_light / hard_light / overlay
+ * Per sample (libImaging/Paste.c, Chops.c), in integers unless said otherwise:
+ *     PASTE under mask m   t = a (255 - m) + b m + 128; ((t >> 8) + t) >> 8      (one division, not two)
+ *     MULTIPLY  a b / 255        SCREEN  255 - (255 - a) (255 - b) / 255          DIFFERENCE  |a - b|
+ *     ADD       float32 (a + b) / scale + offset: a correctly rounded division, then an addition; 0 at or below 0, 255 at
+ *               or above 255, truncated between.  SUBTRACT: (a - b) likewise.  (Where the quotient leaves int's range Pillow
+ *               is undefined; here it saturates.)
+ *     ADD_MODULO (a + b) mod 256   SUBTRACT_MODULO (a - b) mod 256
+ *     SOFT_LIGHT  (255 - a) (a b) / 65536 + a (255 - (255 - a) (255 - b) / 255) / 255
+ *     HARD_LIGHT  b < 128 ? a b / 127 : 255 - (255 - b) (255 - a) / 127;  OVERLAY: the same with a < 128 as the test
+ * The mask of a PASTE region (mode 'L'; the other ops take TA_MASK_NONE only):
+ *     TA_MASK_NONE      none: b replaces a
+ *     TA_MASK_CONSTANT  Image.new('L', size, mask_value), mask_value 0 .. 255
+ *     TA_MASK_BITMAP    the packed w x h bitmap at byte offset mask_value of the HOST buffer `masks`; any number of
+ *                       regions may name one bitmap; the buffer travels in the staging copy of the regions
+ *     TA_MASK_FRAMES    band mask_band (0 .. 2) of the equally sized box at (mask_x, mask_y) of frame mask_frame of
+ *                       `mask_frames`: getchannel(band)
+ * The destination box is as ta_frames_point takes it (half-open, inside the frame, no side longer than 16384); `src` and
+ * `mask_frames` may have any n, h, w.  Regions of one destination frame apply in list order where they overlap (rounds of
+ * pairwise disjoint regions, one launch per round).  `src` and `mask_frames` may be `dst` itself only if no frame that any
+ * region writes is read by any region as its source or mask frame.  All batches must live on `ctx`'s device; the call
+ * runs on `ctx`'s stream and returns when it is done.  n = 0: TA_OK.
+ * TA_E_INVALID, before any launch and any changed pixel, naming the region: what ta_frames_point refuses of a box; a
+ * source or mask box that is not inside its frame; a frame index out of range; an unknown op or mask kind; a mask on an op
+ * other than PASTE; alpha that is NaN or infinite, or 0 as the scale of ADD / SUBTRACT; a mask_value outside 0 .. 255
+ * (CONSTANT); a band outside 0 .. 2; a bitmap that reaches past mask_bytes; `masks` or `mask_frames` NULL where a region
+ * needs them; a frame both written and read as said above. */
+#define TA_COMBINE_PASTE 0
+#define TA_COMBINE_BLEND 1
+#define TA_COMBINE_LIGHTER 2
+#define TA_COMBINE_DARKER 3
+#define TA_COMBINE_DIFFERENCE 4
+#define TA_COMBINE_MULTIPLY 5
+#define TA_COMBINE_SCREEN 6
+#define TA_COMBINE_ADD 7
+#define TA_COMBINE_SUBTRACT 8
+#define TA_COMBINE_ADD_MODULO 9
+#define TA_COMBINE_SUBTRACT_MODULO 10
+#define TA_COMBINE_SOFT_LIGHT 11
+#define TA_COMBINE_HARD_LIGHT 12
+#define TA_COMBINE_OVERLAY 13
+#define TA_MASK_NONE 0
+#define TA_MASK_CONSTANT 1
+#define TA_MASK_BITMAP 2
+#define TA_MASK_FRAMES 3
+typedef struct ta_combine_region {
+  int32_t frame;         /* image index in `dst`                      */
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  int32_t src_frame, src_x, src_y; /* the source box's frame and top-left corner in `src` */
+  int32_t op;            /* TA_COMBINE_*                              */
+  float alpha;           /* BLEND: Image.blend's alpha; ADD, SUBTRACT: scale */
+  int32_t offset;        /* ADD, SUBTRACT                             */
+  int32_t mask_kind;     /* TA_MASK_* (PASTE)                         */
+  int32_t mask_value;    /* CONSTANT: 0 .. 255; BITMAP: byte offset in `masks` */
+  int32_t mask_frame, mask_x, mask_y, mask_band; /* FRAMES            */
+} ta_combine_region;
+int ta_frames_combine(ta_ctx* ctx, ta_frames* dst, const ta_frames* src, const ta_frames* mask_frames,
+                      const ta_combine_region* regions, int n, const uint8_t* masks, size_t mask_bytes);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart

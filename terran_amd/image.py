@@ -36,6 +36,10 @@ Pixel values: `histogram_frames` / `frame_stats` are Pillow's `Image.histogram` 
 `solarize_frames` change resident frames in place with the pixels of `Image.point`, `ImageOps` and `ImageEnhance`, bit
 for bit (`ta_frames_point`, `ta_frames_saturate`): at most one histogram call, tables built on the host by the `*_lut`
 functions (usable without a device), and one in-place call per batch.
+
+Two batches: `paste_frames`, `composite_frames`, `blend_frames`, `chop_frames` / `difference_frames` and `copy_frames` are
+Pillow's `Image.paste`, `Image.composite`, `Image.blend` and the two-image `ImageChops` functions between resident frames
+(`ta_frames_combine`), in place and bit for bit; `pack_combine` builds their records without a device.
 """
 import os
 from pathlib import Path
@@ -727,6 +731,197 @@ def posterize_frames(frames, bits, ctx=None):
 def solarize_frames(frames, threshold=128, ctx=None):
     """`ImageOps.solarize(im, threshold)` of every resident frame, in place."""
     return point_frames(frames, solarize_lut(threshold), ctx=ctx)
+
+
+# ---- two images: paste, composite, blend, ImageChops --------------------------------------------------------------------
+def _int_rows(value, n, widths, what, who):
+    """`value` as an int64 (n, k) array, k in `widths`: one row for all frames, or one per frame."""
+    try:
+        a = np.asarray(value)
+        ok = a.dtype.kind in 'iuf' and a.ndim in (1, 2) and a.shape[-1] in widths and np.array_equal(a, a.astype(np.int64))
+    except (TypeError, ValueError):
+        ok = False
+    if ok and a.ndim == 2 and len(a) != n:
+        ok = False
+    if not ok:
+        raise ValueError('%s: %s must be %s integers, one such row for all frames or one for each of the %d frames'
+                         % (who, what, ' or '.join(str(k) for k in widths), n))
+    return np.broadcast_to(a.astype(np.int64), (n, a.shape[-1]))
+
+
+def pack_combine(frames_shape, other_shape, op='paste', box=None, source=(0, 0), mask=None, mask_band=0, alpha=0.0, offset=0,
+                 shape='box'):
+    """Host only: the records of one `Frames.combine` call -> (lib.COMBINE_DT array, uint8 buffer of packed bitmaps or None).
+    `frames_shape`, `other_shape`: the (N, H, W, 3) of the batch written and of the batch read, which has N frames or one
+    (then every frame reads it).  `op`: a name of lib.COMBINE_OPS or its code.  `box`: None (the corner (0, 0)), Pillow's
+    (x, y), where the piece of `other` right and below `source` goes, or (x0, y0, x1, y1), whose size the piece takes; one
+    for all frames or one per frame, and `source` = (x, y) in `other` likewise.  The box is clipped against the frame with
+    the source shifted accordingly, as Image.paste clips; a frame whose box is empty then gets no record.  `mask` ('paste'
+    only): None, an int 0 .. 255, a uint8 (h, w) array of the unclipped box's size (packed once per distinct clipping), or
+    the (M, h, w, 3) shape of a resident mask batch of M = N or one frames at least as large as the box, read in band
+    `mask_band` from its corner.  `alpha`: Image.blend's, or the scale of 'add' / 'subtract'; `offset`: theirs."""
+    who = 'pack_combine'
+    n, H, W = (int(v) for v in frames_shape[:3])
+    m, oh, ow = (int(v) for v in other_shape[:3])
+    if m not in (1, n):
+        raise ValueError('%s: other must have one frame or %d, got %d' % (who, n, m))
+    code = lib.COMBINE_OPS.get(op.lower()) if isinstance(op, str) else op if op in lib.COMBINE_OPS.values() else None
+    if code is None:
+        raise ValueError('%s: op must be one of %s, got %r' % (who, sorted(lib.COMBINE_OPS), op))
+    if shape not in _SHAPES:
+        raise ValueError("%s: shape must be 'box' or 'ellipse', got %r" % (who, shape))
+    a = _factor(alpha, who)
+    if code in (lib.COMBINE_ADD, lib.COMBINE_SUBTRACT) and a == 0:
+        raise ValueError('%s: scale must not be 0' % who)
+    if isinstance(offset, bool) or not isinstance(offset, (int, np.integer)) or abs(int(offset)) >= 2 ** 31:
+        raise ValueError('%s: offset must be an int, got %r' % (who, offset))
+    boxes = _int_rows((0, 0) if box is None else box, n, (2, 4), 'box', who)
+    sources = _int_rows(source, n, (2,), 'source', who)
+    kind, value, bitmap, mask_frames = lib.MASK_NONE, 0, None, 1
+    if mask is not None:
+        if code != lib.COMBINE_PASTE:
+            raise ValueError("%s: only 'paste' takes a mask" % who)
+        if isinstance(mask, (int, np.integer)) and not isinstance(mask, bool):
+            if not 0 <= int(mask) <= 255:
+                raise ValueError('%s: a constant mask must be within 0 .. 255, got %r' % (who, mask))
+            kind, value = lib.MASK_CONSTANT, int(mask)
+        elif isinstance(mask, np.ndarray) and mask.ndim == 2 and mask.dtype == np.uint8:
+            kind, bitmap = lib.MASK_BITMAP, mask
+        elif isinstance(mask, (tuple, list)) and len(mask) == 4:
+            kind, mask_frames = lib.MASK_FRAMES, int(mask[0])
+            if mask_frames not in (1, n) or mask_band not in (0, 1, 2):
+                raise ValueError('%s: a mask batch must have one frame or %d, and its band be 0, 1 or 2' % (who, n))
+        else:
+            raise ValueError('%s: mask must be None, an int, a uint8 (h, w) array or the shape of a resident batch' % who)
+    rows, packed, at = [], {}, 0
+    for i in range(n):
+        sx, sy = (int(v) for v in sources[i])
+        x0, y0 = int(boxes[i][0]), int(boxes[i][1])
+        pw, ph = (int(boxes[i][2]) - x0, int(boxes[i][3]) - y0) if boxes.shape[1] == 4 else (ow - sx, oh - sy)
+        if pw <= 0 or ph <= 0 or sx < 0 or sy < 0 or sx + pw > ow or sy + ph > oh:
+            raise ValueError('%s: the %d x %d piece at (%d, %d) is empty or not inside the %d x %d other' % (who, pw, ph, sx, sy, ow, oh))
+        if bitmap is not None and bitmap.shape != (ph, pw):
+            raise ValueError('%s: the mask is %s, the pasted piece (%d, %d)' % (who, bitmap.shape, ph, pw))
+        if kind == lib.MASK_FRAMES and (int(mask[1]) < ph or int(mask[2]) < pw):
+            raise ValueError('%s: the mask batch is smaller than the pasted piece' % who)
+        cx0, cy0, cx1, cy1 = max(x0, 0), max(y0, 0), min(x0 + pw, W), min(y0 + ph, H)
+        if cx1 <= cx0 or cy1 <= cy0:
+            continue
+        dx, dy = cx0 - x0, cy0 - y0
+        if bitmap is not None:
+            key = (dx, dy, cx1 - cx0, cy1 - cy0)
+            if key not in packed:
+                packed[key] = (at, np.ascontiguousarray(bitmap[dy:dy + cy1 - cy0, dx:dx + cx1 - cx0]).reshape(-1))
+                at += packed[key][1].size
+            value = packed[key][0]
+        rows.append((i, cx0, cy0, cx1, cy1, _SHAPES[shape], i if m > 1 else 0, sx + dx, sy + dy, code, a, int(offset), kind, value,
+                     i if mask_frames > 1 else 0, dx, dy, int(mask_band) if kind == lib.MASK_FRAMES else 0))
+    masks = np.concatenate([v[1] for v in packed.values()]) if packed else None
+    return np.array(rows, lib.COMBINE_DT), masks
+
+
+def _partners(batches, other, what, who):
+    """-> per batch the batch it is combined with: `other` is one batch (of one frame when `frames` is a list: every frame
+    reads it) or a list with a batch of one frame or as many for every batch of `frames`."""
+    if isinstance(other, lib.Frames):
+        if len(batches) > 1 and other.shape[0] != 1:
+            raise ValueError('%s: %s must be a one-frame batch, or a list like frames' % (who, what))
+        others = [other] * len(batches)
+    elif isinstance(other, (list, tuple)) and len(other) == len(batches) and all(isinstance(o, lib.Frames) for o in other):
+        others = list(other)
+    else:
+        raise ValueError('%s: %s must be a lib.Frames batch or a list of %d of them' % (who, what, len(batches)))
+    for b, o in zip(batches, others):
+        if o.shape[0] not in (1, b.shape[0]):
+            raise ValueError('%s: %s has %d frames for a batch of %d' % (who, what, o.shape[0], b.shape[0]))
+    return others
+
+
+def _combine(who, frames, other, op, box=None, source=(0, 0), mask=None, mask_band=0, alpha=0.0, offset=0, shape='box',
+             same_size=False, ctx=None):
+    """Every batch of `frames` with its partner: everything is packed and checked before anything is launched."""
+    batches, _ = _batches(frames, who)
+    others = _partners(batches, other, 'other', who)
+    resident = isinstance(mask, lib.Frames) or (isinstance(mask, (list, tuple)) and mask and isinstance(mask[0], lib.Frames))
+    mattes = _partners(batches, mask, 'mask', who) if resident else [None] * len(batches)
+    total = sum(b.shape[0] for b in batches)
+    per_frame = [np.ndim(v) == 2 for v in (box, source)]
+    for v, each, what in ((box, per_frame[0], 'box'), (source, per_frame[1], 'source')):
+        if each and len(v) != total:
+            raise ValueError('%s: one %s for each of the %d frames' % (who, what, total))
+    plans, at = [], 0
+    for b, o, mt in zip(batches, others, mattes):
+        n = b.shape[0]
+        if same_size and (o.shape[1:3] != b.shape[1:3] or (mt is not None and mt.shape[1:3] != b.shape[1:3])):
+            raise ValueError('%s: frames of %s need an other and a mask of that size' % (who, b.shape[1:3]))
+        bx = np.asarray(box)[at:at + n] if per_frame[0] else box
+        so = np.asarray(source)[at:at + n] if per_frame[1] else source
+        at += n
+        if n:
+            plans.append((b, o, mt) + pack_combine(b.shape, o.shape, op, bx, so, mt.shape if mt is not None else mask, mask_band,
+                                                   alpha, offset, shape))
+    for b, o, mt, regions, masks in plans:
+        if len(regions):
+            b.combine(o, regions, masks, mask_frames=mt, ctx=ctx)
+    return frames
+
+
+def copy_frames(frames, ctx=None):
+    """A NEW resident batch (or list of them) with the pixels of `frames`: allocated, then pasted into on the device."""
+    batches, listed = _batches(frames, 'copy_frames')
+    outs = []
+    for b in batches:
+        c = ctx if ctx is not None else b.ctx
+        n, h, w = b.shape[:3]
+        out = lib.Frames.zeros(c, n, h, w)
+        if n:
+            out.combine(b, pack_combine(b.shape, b.shape)[0], ctx=c)
+        outs.append(out)
+    return outs if listed else outs[0]
+
+
+def paste_frames(frames, other, box=None, mask=None, source=(0, 0), mask_band=0, ctx=None):
+    """Pillow's `frame.paste(other_frame, box, mask)` for every resident frame, in place (`ta_frames_combine`, one call per
+    batch); returns `frames`.  `frames`: a `lib.Frames` batch or a list of them; `other`: a batch with one frame (pasted
+    into every frame) or as many as `frames`, or a list of such batches, one per batch of `frames`.  `box`: None, (x, y) or
+    (x0, y0, x1, y1), one for all frames or one per frame; it may leave the frame and is clipped as Image.paste clips.
+    `source`: the corner in `other` of the piece that is pasted (default: all of it).  `mask`: None, an int 0 .. 255 (a
+    constant 'L' mask), a host uint8 (h, w) array of the piece's size, or a resident batch (a list of them for a list of
+    frames) whose band `mask_band` is the mask."""
+    return _combine('paste_frames', frames, other, 'paste', box, source, mask, mask_band, ctx=ctx)
+
+
+def composite_frames(frames, other, mask, mask_band=0, ctx=None):
+    """`Image.composite(other, frame, mask)` written into every resident frame, in place: `other` where the mask is 255,
+    the frame where it is 0, blended between.  `other` and `mask` (paste_frames' kinds) have the frames' size."""
+    return _combine('composite_frames', frames, other, 'paste', None, (0, 0), mask, mask_band, same_size=True, ctx=ctx)
+
+
+def blend_frames(frames, other, alpha, ctx=None):
+    """`Image.blend(frame, other, alpha)` of every resident frame, in place: a cross-fade; alpha outside 0 .. 1 extrapolates
+    and clips."""
+    return _combine('blend_frames', frames, other, 'blend', alpha=alpha, same_size=True, ctx=ctx)
+
+
+def chop_frames(frames, other, op, scale=1.0, offset=0, boxes=None, shape='box', ctx=None):
+    """`ImageChops.<op>(frame, other)` of every resident frame, in place: `op` one of 'lighter', 'darker', 'difference',
+    'multiply', 'screen', 'add', 'subtract' (with `scale` and `offset`), 'add_modulo', 'subtract_modulo', 'soft_light',
+    'hard_light', 'overlay'.  `boxes`: None, or one half-open (x0, y0, x1, y1) per frame: only that box changes, from the
+    same box of `other`, under `shape` 'ellipse' only the ellipse Pillow draws into it."""
+    who = 'chop_frames'
+    if not isinstance(op, str) or op.lower() not in lib.COMBINE_OPS or op.lower() in ('paste', 'blend'):
+        raise ValueError('%s: op must be one of %s, got %r' % (who, sorted(set(lib.COMBINE_OPS) - {'paste', 'blend'}), op))
+    if boxes is None:
+        return _combine(who, frames, other, op, alpha=scale, offset=offset, shape=shape, same_size=True, ctx=ctx)
+    batches, _ = _batches(frames, who)
+    q = np.concatenate(_frame_boxes(batches, boxes, who))
+    return _combine(who, frames, other, op, q, q[:, :2], alpha=scale, offset=offset, shape=shape, same_size=True, ctx=ctx)
+
+
+def difference_frames(frames, other, ctx=None):
+    """`ImageChops.difference(frame, other)` of every resident frame, in place: |frame - other|, the motion between two
+    clips when `other` holds the frames before."""
+    return chop_frames(frames, other, 'difference', ctx=ctx)
 
 
 # ---- neighbourhood filters: Image.filter --------------------------------------------------------------------------------

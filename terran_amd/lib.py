@@ -64,6 +64,7 @@ SIGNATURES = {
     'ta_frames_saturate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_frames_filter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     'ta_filter_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'ta_frames_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -164,6 +165,20 @@ FILTER_SPEC_DT = np.dtype([('kind', '<i4'), ('size', '<i4'), ('rank', '<i4'), ('
                            ('scale', '<f4'), ('offset', '<f4'), ('factor', '<f4'), ('radius', '<f4'), ('percent', '<i4'),
                            ('threshold', '<i4')])
 assert FILTER_SPEC_DT.itemsize == 140
+
+# ta_combine_region (include/terran_amd.h), the ops TA_COMBINE_* and the mask kinds TA_MASK_*; shapes: BLUR_*
+(COMBINE_PASTE, COMBINE_BLEND, COMBINE_LIGHTER, COMBINE_DARKER, COMBINE_DIFFERENCE, COMBINE_MULTIPLY, COMBINE_SCREEN, COMBINE_ADD,
+ COMBINE_SUBTRACT, COMBINE_ADD_MODULO, COMBINE_SUBTRACT_MODULO, COMBINE_SOFT_LIGHT, COMBINE_HARD_LIGHT, COMBINE_OVERLAY) = range(14)
+COMBINE_OPS = {'paste': COMBINE_PASTE, 'blend': COMBINE_BLEND, 'lighter': COMBINE_LIGHTER, 'darker': COMBINE_DARKER,
+               'difference': COMBINE_DIFFERENCE, 'multiply': COMBINE_MULTIPLY, 'screen': COMBINE_SCREEN, 'add': COMBINE_ADD,
+               'subtract': COMBINE_SUBTRACT, 'add_modulo': COMBINE_ADD_MODULO, 'subtract_modulo': COMBINE_SUBTRACT_MODULO,
+               'soft_light': COMBINE_SOFT_LIGHT, 'hard_light': COMBINE_HARD_LIGHT, 'overlay': COMBINE_OVERLAY}
+MASK_NONE, MASK_CONSTANT, MASK_BITMAP, MASK_FRAMES = 0, 1, 2, 3
+COMBINE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                       ('src_frame', '<i4'), ('src_x', '<i4'), ('src_y', '<i4'), ('op', '<i4'), ('alpha', '<f4'), ('offset', '<i4'),
+                       ('mask_kind', '<i4'), ('mask_value', '<i4'), ('mask_frame', '<i4'), ('mask_x', '<i4'), ('mask_y', '<i4'),
+                       ('mask_band', '<i4')])
+assert COMBINE_DT.itemsize == 72
 
 
 def filter_plan(regions, specs):
@@ -691,6 +706,20 @@ class Frames:
         regions, p, n = _records(regions, FILTER_REGION_DT)
         specs = np.ascontiguousarray(specs, dtype=FILTER_SPEC_DT).reshape(-1)
         ctx.check(ctx.lib.ta_frames_filter(ctx.h, self.h, p, n, ptr(specs) if len(specs) else None, len(specs)))
+
+    def combine(self, src, regions, masks=None, mask_frames=None, ctx=None):
+        """Combine `regions` (a COMBINE_DT array, in order) of this batch with their source boxes in the batch `src`, in
+        place (ta_frames_combine): Pillow's paste under a mask, Image.blend or an ImageChops function of each half-open box,
+        pasted back under its shape.  `masks`: the uint8 buffer that holds the packed bitmaps of the MASK_BITMAP regions,
+        each at the byte offset its `mask_value` names; `mask_frames`: the batch the MASK_FRAMES regions read a band of.
+        `src` and `mask_frames` may be this batch when no frame is both written and read.  `ctx`: the CALLER's, as in `blur`."""
+        ctx = ctx or self.ctx
+        regions, p, n = _records(regions, COMBINE_DT)
+        if masks is not None:
+            masks = np.ascontiguousarray(masks, dtype=np.uint8).reshape(-1)
+        has = masks is not None and len(masks) > 0
+        ctx.check(ctx.lib.ta_frames_combine(ctx.h, self.h, src.h, mask_frames.h if mask_frames is not None else None, p, n,
+                                            ptr(masks) if has else None, len(masks) if has else 0))
 
     def transform(self, regions, out_h, out_w, filter, fill=None, ctx=None):
         """A NEW batch (len(regions), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), method, a,

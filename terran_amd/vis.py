@@ -563,6 +563,75 @@ def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ct
     return frames
 
 
+# ---- two batches: a processed copy inside the face boxes, chips back into the frame ------------------------------------
+def pack_composite(faces_per_frame, shapes, other_frames=None, margin=0.0, shape='box', alpha=None):
+    """-> lib.COMBINE_DT array: pack_blur's regions (the same margin, truncation, clipping and order) as PASTE records that
+    read the same box of the other batch -- frame i of it, or frame 0 when it has `other_frames` = 1 frame; `alpha`: None,
+    or 0 .. 1: a constant mask round(255 alpha).  Host only."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    if alpha is not None and not 0 <= float(alpha) <= 1:
+        raise ValueError('alpha must be None or within 0 .. 1, got %r' % (alpha,))
+    boxes = _clipped_boxes(faces_per_frame, shapes, margin)
+    q = np.zeros(len(boxes), lib.COMBINE_DT)
+    for r, (f, _, x0, y0, x1, y1) in zip(q, boxes):
+        r['frame'], r['x0'], r['y0'], r['x1'], r['y1'], r['shape'] = f, x0, y0, x1, y1, BLUR_SHAPES[shape]
+        r['src_frame'], r['src_x'], r['src_y'], r['op'] = 0 if other_frames == 1 else f, x0, y0, lib.COMBINE_PASTE
+        if alpha is not None:
+            r['mask_kind'], r['mask_value'] = lib.MASK_CONSTANT, int(round(255 * float(alpha)))
+    return q
+
+
+def composite_faces(frames, other, faces_per_frame, margin=0.0, shape='box', alpha=None, ctx=None):
+    """Give every face box of the resident batch `frames` the pixels of `other`, in place: `other` a batch of the frames'
+    size, with as many frames or one -- a denoised, blurred or equalised copy that is to show only in the faces.  The
+    boxes, their clipping and their order are blur_faces'; `alpha`: None pastes, a float 0 .. 1 blends under the constant
+    mask round(255 alpha), as Pillow's paste does."""
+    _check_batch(frames, faces_per_frame)
+    if other.shape[1:3] != frames.shape[1:3] or other.shape[0] not in (1, frames.shape[0]):
+        raise ValueError('composite_faces: other must be %s frames, one or %d, got %s' % (frames.shape[1:3], frames.shape[0], other.shape))
+    frames.combine(other, pack_composite(faces_per_frame, frames.shape, other.shape[0], margin, shape, alpha), ctx=ctx)
+    return frames
+
+
+def pack_insets(index, chips_shape, shapes, origin=(8, 8), gap=4):
+    """-> lib.COMBINE_DT array: chip k of a (n, h, w, 3) chip batch, which belongs to frame index[k][0], pasted into that
+    frame: each frame's chips in a row from `origin` = (x, y), `gap` pixels apart, a new row below at the frame's right
+    edge; a chip that no longer fits into the frame is left out.  Host only."""
+    n, ch, cw = (int(v) for v in chips_shape[:3])
+    index = np.asarray(index, np.int64).reshape(-1, 2)
+    if len(index) != n:
+        raise ValueError('%d index pairs for %d chips' % (len(index), n))
+    ox, oy, gap = int(origin[0]), int(origin[1]), int(gap)
+    if ox < 0 or oy < 0 or gap < 0:
+        raise ValueError('origin and gap must not be negative, got %r, %r' % (origin, gap))
+    frames = int(index[:, 0].max()) + 1 if n else 0
+    sizes = _frame_sizes(shapes, frames)
+    rows, at = [], {}
+    for k, f in enumerate(int(v) for v in index[:, 0]):
+        if f < 0:
+            raise ValueError('frame %d in the index' % f)
+        h, w = int(sizes[f][0]), int(sizes[f][1])
+        x, y = at.get(f, (ox, oy))
+        if x + cw > w and x != ox:
+            x, y = ox, y + ch + gap
+        at[f] = (x, y)
+        if x + cw > w or y + ch > h:
+            continue
+        rows.append((f, x, y, x + cw, y + ch, lib.BLUR_BOX, k, 0, 0, lib.COMBINE_PASTE, 0.0, 0, lib.MASK_NONE, 0, 0, 0, 0, 0))
+        at[f] = (x + cw + gap, y)
+    return np.array(rows, lib.COMBINE_DT)
+
+
+def inset_chips(frames, chips, index, origin=(8, 8), gap=4, ctx=None):
+    """Paste the chips that `crop_faces` / `align_faces` cut (`chips`, `index` as they return them) back into their frames
+    of the resident batch `frames` as thumbnails, in place; the layout is pack_insets'."""
+    if chips is None or not len(index):
+        return frames
+    frames.combine(chips, pack_insets(index, chips.shape, frames.shape, origin, gap), ctx=ctx)
+    return frames
+
+
 def pack_filter(faces_per_frame, shapes, margin=0.0, shape='box'):
     """-> lib.FILTER_REGION_DT array: pack_blur's regions (the same margin, truncation, clipping and order) for
     Frames.filter, every one with spec 0.  Host only."""
