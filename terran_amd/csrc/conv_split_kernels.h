@@ -576,6 +576,9 @@ static void split_launch_facts(ta_ctx* ctx, ta_conv_launch& q, const ta_tile_gri
   bool ok = lean_ok && q.out_fmt == split_fmt && (q.cout & 7) == 0 && ((q.out_ch | q.res_ch | q.o2_ch) & 7) == 0 && fits(q.out_img, q.out_off0);
   if (q.res) ok = ok && q.res_fmt == split_fmt && fits(q.res_img, q.res_off0);
   if (q.out2) ok = ok && q.o2_fmt == split_fmt && fits(q.o2_img, q.o2_off0);
+  // ... and one of the shapes conv_drain_dispatch is compiled for: every other launch takes the generic drain and is not counted
+  const bool plain = !q.res && !q.out2;
+  ok = ok && (q.pool ? (plain && q.act == TA_ACT_RELU) : (q.bias9 ? (plain && q.act == TA_ACT_PRELU) : (plain || (q.res && q.act == TA_ACT_NONE))));
   q.fast_drain = ok ? 1 : 0;
   if (ok) ctx->conv_counts[TA_CV_COUNT - 1] += 1;     // slot 15: launches whose epilogue ran the specialised drain
 }

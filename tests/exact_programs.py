@@ -9,7 +9,9 @@ The rule (`reference` asserts it, DESIGN.md states it): every value a program ho
 that make it is an integer of at most 16 significant bits -- what a bf16 hi + lo pair carries (the half-float pair carries
 22) -- and at most 65504, the end of the half-float range for the tensors the packer stores unscaled.  A tensor that is
 only ever held as float32 (pinned f32 and read by no op, or inside the all-float32 front kernel) may reach 2^24.  The
-bound is taken over sum |w| |x| + |b|, so it holds for every summation order a kernel may choose.
+bound is taken over sum |w| |x| + |b|, so it holds for every summation order a kernel may choose.  Through a conv's output stage
+it is carried on: times max(1, |slope|) of an integer PReLU slope, plus |shortcut|, and times |scale2| plus |shift2| (integers)
+into the second output, each against the limit of the tensor it lands in.
 
 Every program is of kind MODEL_RETINAFACE unless said otherwise: its preprocess writes BGR integers 0..255 as float32, 4th
 channel 0, into the tensor named 'input'.  A SELECTOR conv (1x1 or 3x3, integer weights and bias) turns that into an exactly
@@ -129,6 +131,7 @@ class Net:
         self.tid = {}
         self.steps = []
         self.mid_ops = {}                                         # dst name -> op index of a dw+pw block
+        self.conv_ops = {}                                        # dst name -> op index of the last conv that writes it
         t0 = P.tensor(4, in_halo, alias_of=-2 if shape_only_input else -1, name='input')
         self.tid['input'] = t0
         P.input_tensor = t0
@@ -138,9 +141,23 @@ class Net:
         self.tid[name] = self.P.tensor(c, halo, name=name, f32=f32)
         return name
 
-    def conv(self, src, dst, W, b, *, stride=1, pad=None, relu=False, pool=False):
-        self.P.conv(self.tid[src], self.tid[dst], W, b, stride=stride, pad=pad, act=pack.ACT_RELU if relu else pack.ACT_NONE, pool=pool)
-        self.steps.append(('conv', src, dst, dict(W=W, b=b, stride=stride, pad=W.shape[2] // 2 if pad is None else pad, relu=relu, pool=pool)))
+    def conv(self, src, dst, W, b, *, stride=1, pad=None, relu=False, pool=False, prelu=None, res=None, res_ch_off=0, res_up2=0,
+             out2=None, out2_ch_off=0, scale2=None, shift2=None, out_ch_off=0, in_ch_off=0, cin_p=None, groups=1, k_split=0,
+             in_affine=None, variant=0):
+        """pack.Program.conv with tensors by name.  The output stage in the kernels' order: conv + bias (in_affine: of scale * x +
+        shift, zero-padded AFTER the affine), ReLU / PReLU, + res[:, res_ch_off:+cout, y >> res_up2, x >> res_up2], store into the
+        slice at out_ch_off, then out2[:, out2_ch_off:+cout] = out * scale2 + shift2."""
+        act = pack.ACT_PRELU if prelu is not None else (pack.ACT_RELU if relu else pack.ACT_NONE)
+        tid = lambda n: -1 if n is None else self.tid[n]
+        self.conv_ops[dst] = len(self.P.ops)
+        self.P.conv(self.tid[src], self.tid[dst], W, b, stride=stride, pad=pad, act=act, pool=pool, prelu=prelu, res=tid(res),
+                    res_ch_off=res_ch_off, res_up2=res_up2, out2=tid(out2), out2_ch_off=out2_ch_off, scale2=scale2, shift2=shift2,
+                    out_ch_off=out_ch_off, in_ch_off=in_ch_off, cin_p=cin_p, groups=groups, k_split=k_split, in_affine=in_affine,
+                    variant=variant)
+        self.steps.append(('conv', src, dst, dict(W=W, b=b, stride=stride, pad=W.shape[2] // 2 if pad is None else pad, relu=relu, pool=pool,
+                                                  prelu=prelu, res=res, res_ch_off=res_ch_off, res_up2=res_up2, out2=out2,
+                                                  out2_ch_off=out2_ch_off, scale2=scale2, shift2=shift2, out_ch_off=out_ch_off,
+                                                  in_ch_off=in_ch_off, groups=groups, k_split=k_split, in_affine=in_affine)))
 
     def dwconv(self, src, dst, W, b, *, stride=1, relu=True):
         self.P.dwconv(self.tid[src], self.tid[dst], W, b, stride=stride, relu=relu)
@@ -179,21 +196,114 @@ class Net:
         return LIMIT_F32 if self.tid[name] in self.P.f32_only and not self.read_by_an_op(name) else LIMIT_SPLIT
 
 
-def reference(net, fr):
+MISTAKES = ('up2_unshifted', 'res_ch_off+4', 'out2_ch_off+8', 'prelu_shifted', 'corner_as_edge', 'k_range_dropped', 'no_shift2')
+
+
+def border_class(n):
+    """Per axis: first 0, middle 1, last 2, the only one 3 (csrc/conv_common.h: ta_border_class; class = 4 cy + cx)."""
+    c = np.ones(n, np.int64)
+    c[0], c[-1] = 0, 2
+    return c if n > 1 else np.array([3])
+
+
+def k_range_mask(W, k_split, r):
+    """True where weight W[o, c, ky, kx] lies in K range `r` of `k_split`: K runs (tap, channel), in slabs of 32, range r is slabs
+    [r n / k_split, (r + 1) n / k_split)."""
+    _, cin, kh, kw = W.shape
+    n = kh * kw * cin // 32
+    kidx = np.arange(kh * kw * cin)
+    m = (kidx >= r * n // k_split * 32) & (kidx < (r + 1) * n // k_split * 32)
+    return m.reshape(kh, kw, cin).transpose(2, 0, 1)[None]
+
+
+def _conv_step(net, ref, x, dst, a, lim, chans, mistake):
+    """One conv of `reference` with its whole output stage.  Returns what `dst` holds afterwards; writes `out2` into ref itself.
+    `mistake`: one of MISTAKES (the deliberately wrong references of tests/test_exact_programs_cpu.py), or 'fold': in_affine by the
+    packer's folded weights and border-class biases instead of by its meaning."""
+    strict = mistake is None
+    W, b, g = np.asarray(a['W'], np.float64), np.asarray(a['b'], np.float64), a['groups']
+    cout, cin = W.shape[:2]
+    xin = x[:, a['in_ch_off']:a['in_ch_off'] + cin * g]
+    assert xin.shape[1] == cin * g
+    xabs = np.abs(xin)
+    if a['k_split'] > 1 and mistake == 'k_range_dropped':
+        W = W * ~k_range_mask(W, a['k_split'], 1)
+    aff = a['in_affine']
+    if aff is not None and mistake in ('fold', 'corner_as_edge'):
+        Wf, b16 = pack.fold_input_affine(W, b, *aff)
+        y = conv_ref(xin, Wf, np.zeros(cout), 1, 1)
+        cy, cx = border_class(y.shape[2]), border_class(y.shape[3])
+        cls = 4 * cy[:, None] + cx[None, :]
+        if mistake == 'corner_as_edge':
+            cls = np.where((cy[:, None] != 1) & (cx[None, :] != 1), 4 * cy[:, None] + 1, cls)
+        y = y + np.transpose(b16[cls], (2, 0, 1))[None]
+        aff = None
+    elif aff is not None:
+        sc, sh = (np.asarray(v, np.float64)[None, :, None, None] for v in aff)
+        xin, xabs = xin * sc + sh, xabs * np.abs(sc) + np.abs(sh)                       # bounds the folded form as well
+    if aff is not None or a['in_affine'] is None:
+        cg, og = cin, cout // g
+        y = np.concatenate([conv_ref(xin[:, i * cg:(i + 1) * cg], W[i * og:(i + 1) * og], b[i * og:(i + 1) * og], a['stride'], a['pad'])
+                            for i in range(g)], axis=1)
+    cg, og = cin, cout // g
+    bound = np.concatenate([conv_ref(xabs[:, i * cg:(i + 1) * cg], np.abs(W[i * og:(i + 1) * og]), np.abs(b[i * og:(i + 1) * og]),
+                                     a['stride'], a['pad']) for i in range(g)], axis=1)
+    if strict:
+        _exact(dst, bound, lim)
+    if a['prelu'] is not None:
+        slope = np.asarray(a['prelu'], np.float64)
+        assert np.array_equal(slope, np.rint(slope)), 'PReLU slopes are integers here'
+        bound = bound * np.maximum(1.0, np.abs(slope))[None, :, None, None]
+        if mistake == 'prelu_shifted':
+            slope = np.roll(slope, 1)
+        y = np.where(y > 0, y, y * slope[None, :, None, None])
+    elif a['relu']:
+        y = np.maximum(y, 0.0)
+    if a['pool']:
+        y, bound = pool_ref(y), pool_ref(bound)
+    if a['res'] is not None:
+        r = ref[a['res']]
+        off = a['res_ch_off'] + (4 if mistake == 'res_ch_off+4' else 0)
+        r = r[:, (off + np.arange(cout)) % r.shape[1]]
+        if a['res_up2']:
+            iy, ix = np.arange(y.shape[2]) >> 1, np.arange(y.shape[3]) >> 1
+            assert r.shape[2:] == ((y.shape[2] + 1) // 2, (y.shape[3] + 1) // 2)
+            if mistake == 'up2_unshifted':
+                iy, ix = np.minimum(np.arange(y.shape[2]), r.shape[2] - 1), np.minimum(np.arange(y.shape[3]), r.shape[3] - 1)
+            r = r[:, :, iy][:, :, :, ix]
+        assert r.shape == y.shape, (dst, r.shape, y.shape)
+        y, bound = y + r, bound + np.abs(r)
+    if strict:
+        _exact(dst, bound, lim)
+    if a['out2'] is not None:
+        s2, h2 = (np.asarray(v, np.float64)[None, :, None, None] for v in (a['scale2'], a['shift2']))
+        z = y * s2 + (0.0 if mistake == 'no_shift2' else h2)
+        if strict:
+            _exact(a['out2'], bound * np.abs(s2) + np.abs(h2), net.limit(a['out2']))
+            assert np.array_equal(z, np.rint(z)), a['out2']
+        off = a['out2_ch_off'] + (8 if mistake == 'out2_ch_off+8' else 0)
+        full = ref[a['out2']].copy() if a['out2'] in ref else np.zeros((y.shape[0], chans[a['out2']]) + y.shape[2:])
+        full[:, (off + np.arange(cout)) % full.shape[1]] = z
+        ref[a['out2']] = full
+    if a['out_ch_off'] or cout != chans[dst]:                       # into a slice: every other channel stays what its producer wrote
+        full = ref[dst].copy() if dst in ref else np.zeros((y.shape[0], chans[dst]) + y.shape[2:])
+        assert full.shape[2:] == y.shape[2:], (dst, full.shape, y.shape)
+        full[:, a['out_ch_off']:a['out_ch_off'] + cout] = y
+        y = full
+    return y
+
+
+def reference(net, fr, mistake=None):
     """float64 value of every named tensor of `net` for the uint8 RGB frames `fr`, as (N, C, H, W).  Asserts the exactness rule
-    of the module text on every step.  A dw+pw block also yields '<dst>:mid', its depthwise intermediate."""
+    of the module text on every step.  A dw+pw block also yields '<dst>:mid', its depthwise intermediate.  `mistake`: see
+    _conv_step (the rule is then not asserted: a wrong reference may break it)."""
     ref = {'input': input_ref(fr)}
     chans = {n: net.P.tensors[t][0] for n, t in net.tid.items()}
     for op, src, dst, a in net.steps:
         x = ref[src]
         lim = net.limit(dst)
         if op == 'conv':
-            y = conv_ref(x, a['W'], a['b'], a['stride'], a['pad'])
-            _exact(dst, conv_ref(np.abs(x), np.abs(a['W']), np.abs(a['b']), a['stride'], a['pad']), lim)
-            if a['relu']:
-                y = np.maximum(y, 0.0)
-            if a['pool']:
-                y = pool_ref(y)
+            y = _conv_step(net, ref, x, dst, a, lim, chans, mistake)
         elif op == 'dwconv':
             y = dw_ref(x, a['W'], a['b'], a['stride'])
             _exact(dst, dw_ref(np.abs(x), np.abs(a['W']), np.abs(a['b']), a['stride']), lim)
@@ -222,23 +332,24 @@ def reference(net, fr):
                 y = np.maximum(conv_ref(y, Wp, bp), 0.0)
         else:
             raise AssertionError(op)
-        assert np.array_equal(y, np.rint(y)), dst                   # integers: below the limit they have their bits
-        _exact(dst, np.abs(y), lim)
+        if mistake is None:
+            assert np.array_equal(y, np.rint(y)), dst               # integers: below the limit they have their bits
+            _exact(dst, np.abs(y), lim)
         assert y.shape[1] == chans[dst], (dst, y.shape, chans[dst])
         ref[dst] = y
     return ref
 
 
 # ---- the builders the tests share -----------------------------------------------------------------------------------------------
-def selector(net, rng, name, C, *, k=1, wmax=64, halo=1, relu=False, f32=False, src='input'):
+def selector(net, rng, name, C, *, k=1, wmax=64, halo=1, relu=False, f32=False, src='input', stride=1):
     """'input' -> conv k x k (3 -> C) -> `name`: integers, lo words and signs in use (see selector_weights)."""
     net.tensor(name, C, halo, f32=f32)
     W, b = selector_weights(rng, C, k, wmax if k == 1 else max(1, wmax // 8), density=1.0 if k == 1 else 0.5)
-    net.conv(src, name, W, b, relu=relu)
+    net.conv(src, name, W, b, relu=relu, stride=stride)
     return name
 
 
-def sink(net, rng, src, name, C, cout=64):
+def sink(net, rng, src, name, C, cout=64, variant=0):
     """`src` (halo 1) -> conv 3x3 pad 1 (C -> cout, one +-1 weight per tap and output) -> `name` (float32).  Its border outputs
     read the halo of `src`: exact only while that halo is still zero.  cout = 64 keeps a 32-channel-block `src` pre-split."""
     net.tensor(name, cout, 0, f32=True)
@@ -246,7 +357,7 @@ def sink(net, rng, src, name, C, cout=64):
     for o in range(cout):
         for t in range(9):
             W[o, rng.integers(0, C), t // 3, t % 3] = rng.choice([-1, 1])
-    net.conv(src, name, W, np.zeros(cout))
+    net.conv(src, name, W, np.zeros(cout), variant=variant)
     return name
 
 
@@ -349,6 +460,232 @@ def preprocess_net(kind, precision='f32'):
     W, b = selector_weights(rng, 32, 1, 2)
     net.P.conv(net.tid['input'], net.tid['out'], W, b)             # not a step: only the RetinaFace input is integers
     return net
+
+
+# ---- the conv output stage (tests/test_gpu_conv_exact.py) ------------------------------------------------------------------------
+# Integer conventions on top of the rule of the module text: PReLU slopes are integers of {-2, -1, 0, 2, 3} per channel, the second
+# output's scale is of {-2, -1, 1, 2} and its shift an integer, an input affine has scales of {-1, 1, 2} and integer shifts -- integer
+# times integer stays an integer, and the bound is carried through the whole chain (bound * max(1, |slope|) + |shortcut|, then
+# * |scale2| + |shift2|), each against the limit of the tensor it lands in.
+def stage_weights(rng, cout, cin, k, nz=3, mags=(4, 1, 2, 1), bias=50, ranges=1):
+    """(cout, cin, k, k): `nz` weights of +-mags[o % 4] per output channel o, the j-th of them in K range j % ranges (k_range_mask);
+    integer bias.  The stepped magnitudes give the channels of the output different exponents in the half-float mode."""
+    n = k * k * cin // 32
+    W = np.zeros((cout, k * k * cin))
+    for o in range(cout):
+        for j in range(nz):
+            r = j % ranges
+            W[o, rng.integers(r * n // ranges * 32, (r + 1) * n // ranges * 32)] = rng.choice([-1, 1]) * mags[o % 4]
+    return W.reshape(cout, k, k, cin).transpose(0, 3, 1, 2).copy(), rng.integers(-bias, bias + 1, cout).astype(np.float64)
+
+
+EPILOGUES = {                                   # what the conv under test does behind its sums
+    'plain': dict(),
+    'relu_slices': dict(relu=True, out_slice=True, in_slice=True),     # reads channels 32.. of 'src', writes channels 32.. of 'out'
+    'prelu': dict(prelu=True),
+    'res32': dict(res=32),                                             # + shortcut channels 32..
+    'res0_out2_slice': dict(res=0, out2=32),                           # + shortcut, second output into channels 32.. of 'out2'
+    'prelu_res32_out2': dict(prelu=True, res=32, out2=0),
+    'relu_out2': dict(relu=True, out2=0),
+    'affine_prelu': dict(prelu=True, affine=True),                     # in_affine: nine border-class biases
+    'affine_relu_res0': dict(relu=True, affine=True, res=0),
+}
+ALL_EPI = tuple(EPILOGUES)
+NO_AFFINE = tuple(e for e in EPILOGUES if not e.startswith('affine'))
+
+CONV_CASES = {                                  # C, cout, k, stride, groups, the epilogues run on it
+    'c64_3x3': dict(C=64, cout=64, k=3, epi=ALL_EPI),
+    'c128_3x3': dict(C=128, cout=128, k=3, epi=ALL_EPI),
+    'c64to128_1x1_s2': dict(C=64, cout=128, k=1, stride=2, epi=('plain', 'res0_out2_slice', 'prelu_res32_out2')),
+    'c256_3x3_g2': dict(C=256, cout=256, k=3, groups=2, epi=('relu_slices', 'prelu', 'res32', 'prelu_res32_out2')),
+    # 40 channels at 132 of 192: no 8-channel boundary, so only the generic kernel's direct drain can run it
+    'c128to40in192_1x1': dict(C=128, cout=40, k=1, out_total=192, out_off=132, epi=NO_AFFINE),
+    'c192to128_7x7': dict(C=192, cout=128, k=7, epi=('plain', 'prelu_res32_out2')),
+}
+VARIANTS = ('generic', 'pipe64', 'split_2x2', 'split_1x4', 'split_2x4', 'split_2x2_w2', 'win_2x2')
+SPLIT_VARIANTS = ('split_2x2', 'split_1x4', 'split_2x4', 'split_2x2_w2')
+# (n, h, w) of the OUTPUT map: M = 1 (a single pixel), 45 (several images in one partial tile), 128 (exactly one tile), 132 (a full
+# tile and a tail of 4), 270 (beyond 256, tiles crossing images)
+SIZES = ((1, 1, 1), (3, 5, 3), (2, 8, 8), (1, 11, 12), (3, 9, 10))
+THIN_SIZES = SIZES[1::2] + SIZES[4:]             # 45, 132, 270: what every case runs; the single pixel and the exact tile on two cases
+FULL_SIZE_CASES = ('c128_3x3', 'c128to40in192_1x1')   # every kernel's staged and lean drains, and the direct drain
+AFFINE_SIZE = (1, 6, 1)                        # one column: every pixel is of an 'only' class across and a first / middle / last down
+
+
+def case_sizes(case, affine=False):
+    return (SIZES if case in FULL_SIZE_CASES else THIN_SIZES) + ((AFFINE_SIZE,) if affine else ())
+
+
+def win_patch_rows(h, w, k, BM):
+    """csrc/conv_split.hip: ta_win_patch_rows for an h x w map read through a k x k window (halo k // 2)."""
+    halo = k // 2
+    wp, hp, n = w + 2 * halo, h + 2 * halo, BM - 1
+    return n + -(-n // w) * (wp - w) + -(-n // (h * w)) * (hp - h) * wp + (k - 1) * wp + k
+
+
+def variant_eligible(variant, precision, *, cout, k, stride=1, groups=1, staged=True, k_split=0, size=None, cin=64):
+    """csrc/conv_igemm.hip: variant_eligible, for a conv whose input is float32 under 'generic' and in the precision's own format
+    otherwise (cin % 32 == 0, so K is uniform)."""
+    coutp = -(-cout // 32) * 32
+    deep = k * k * cin // 32 >= 2
+    if variant == 'generic':
+        return groups == 1
+    if not (deep and staged):
+        return False
+    if variant == 'pipe64':
+        return coutp % 64 == 0 and groups == 1
+    if variant in ('split_2x2', 'split_2x4'):
+        return coutp % 128 == 0
+    if variant == 'split_1x4':
+        return coutp % 64 == 0 and (cout // groups) % 64 == 0
+    if variant == 'split_2x2_w2':
+        return coutp % 128 == 0 and k_split <= 1
+    if variant == 'win_2x2':
+        return (precision == 'f16x3' and stride == 1 and k_split <= 1 and k * k >= 4 and coutp % 128 == 0
+                and (size is None or win_patch_rows(size[1], size[2], k, 128) <= 384))
+    raise AssertionError(variant)
+
+
+def conv_programs(case, variant, precision):
+    """[(epilogue, io, sizes)] `variant` can run of CONV_CASES[case] in `precision`.  io 'f32': shortcut and outputs pinned to float32
+    ('generic': the input as well); 'split': every tensor in the precision's pre-split format, where the split-role and window
+    kernels take the lean drain for LEAN_EPILOGUES."""
+    c = CONV_CASES[case]
+    staged = c.get('out_off', 0) % 8 == 0
+    out = []
+    for epi in c['epi']:
+        e = EPILOGUES[epi]
+        sizes = [s for s in case_sizes(case, e.get('affine'))
+                 if variant_eligible(variant, precision, cout=c['cout'], k=c['k'], stride=c.get('stride', 1), groups=c.get('groups', 1),
+                                     staged=staged, size=s, cin=c['C'] // c.get('groups', 1))]
+        for io in ('f32', 'split'):
+            if io == 'split' and (precision == 'f32' or variant == 'generic'):
+                continue
+            if sizes:
+                out.append((epi, io, tuple(sizes)))
+    return out
+
+
+KSPLIT_SIZES = ((3, 5, 3), (1, 11, 12), (3, 9, 10))
+
+
+def frame_seed(size):
+    return 1000 + size[0] * 977 + size[1] * 31 + size[2]
+
+
+def frame_size(size, stride=1):
+    """The frames whose conv output map is `size`."""
+    n, h, w = size
+    return (n, stride * (h - 1) + 1, stride * (w - 1) + 1)
+
+
+def lean_expected(variant, precision, e, io, k_split=0):
+    """Whether the launch runs conv_drain_fast (1) or the generic staged drain (0): a split-role or window kernel outside the f32
+    mode, no K ranges, every tensor of the output stage pre-split, and epilogue `e` (a value of EPILOGUES) one of the shapes
+    conv_drain_dispatch is compiled for -- plain / ReLU / PReLU, no activation + shortcut (+ second output), in_affine + PReLU."""
+    plain = e.get('res') is None and e.get('out2') is None
+    act = bool(e.get('relu') or e.get('prelu'))
+    shape = (plain and bool(e.get('prelu'))) if e.get('affine') else (plain or (e.get('res') is not None and not act))
+    return int((variant in SPLIT_VARIANTS or variant.startswith('win')) and precision != 'f32' and io == 'split' and k_split <= 1 and shape)
+
+
+def _stage(net, rng, c, e, variant, io, *, stride=1, res_from=None, res_up2=0, k_split=0, nz=3, seed_affine=True):
+    """'src' -> the conv under test with epilogue `e` -> 'out' (-> 'out2'), and a sink conv behind each output."""
+    from terran_amd import lib
+    C, cout, k, groups = c['C'], c['cout'], c['k'], c.get('groups', 1)
+    pin = io == 'f32'
+    in_off = 32 if e.get('in_slice') else 0
+    selector(net, rng, 'src', C + in_off, halo=k // 2, wmax=1, f32=variant == 'generic')
+    kw = dict(stride=stride, groups=groups, variant=lib.CONV_VARIANTS[variant], in_ch_off=in_off, k_split=k_split, relu=bool(e.get('relu')))
+    if e.get('res') is not None:
+        selector(net, rng, 'shortcut', cout + 32, k=3, halo=2, wmax=16, f32=pin, stride=2 if res_up2 else stride)
+        kw.update(res='shortcut', res_ch_off=e['res'], res_up2=res_up2)
+    out_total, out_off = c.get('out_total', cout + 64 if e.get('out_slice') else cout), c.get('out_off', 32 if e.get('out_slice') else 0)
+    if out_total != cout:
+        selector(net, rng, 'out', out_total, k=3, halo=1, wmax=16, f32=pin, stride=stride)      # every channel written before
+    else:
+        net.tensor('out', cout, 1, f32=pin)
+    if e.get('out2') is not None:
+        if e['out2']:
+            selector(net, rng, 'out2', cout + 32, k=3, halo=1, wmax=16, f32=pin, stride=stride)
+        else:
+            net.tensor('out2', cout, 1, f32=pin)
+        kw.update(out2='out2', out2_ch_off=e['out2'], scale2=rng.choice([-2, -1, 1, 2], cout).astype(np.float64),
+                  shift2=rng.integers(-100, 101, cout).astype(np.float64))
+    if e.get('prelu'):
+        kw['prelu'] = rng.choice([-2, -1, 0, 2, 3], cout).astype(np.float64)
+    if e.get('affine'):
+        kw['in_affine'] = (rng.choice([-1, 1, 2], C).astype(np.float64), rng.integers(-8, 9, C).astype(np.float64))
+    W, b = stage_weights(rng, cout, C // groups, k, nz=nz, ranges=max(k_split, 1))
+    net.conv('src', 'out', W, b, out_ch_off=out_off, **kw)
+    # the sinks are pinned as well, to another kernel than the one under test: the launch counts then say which conv ran where
+    # (40 or 72 channels are no whole K slabs: those sinks are the generic kernel's, as the conv under test is)
+    net.sink_variant = sv = 'pipe64' if variant != 'pipe64' and cout % 32 == 0 else ('generic' if pin else 'split_1x4')
+    sink(net, rng, 'out', 'after', out_total, variant=lib.CONV_VARIANTS[sv])
+    if e.get('out2') is not None:
+        sink(net, rng, 'out2', 'after2', cout + e['out2'], variant=lib.CONV_VARIANTS[sv])
+    n_sel = sum(1 for s in net.steps if s[1] == 'input')
+    net.counts = {variant: 1}                                       # what Context.conv_counts() must show after one forward
+    for v, n in (('generic', n_sel), (sv, 2 if e.get('out2') is not None else 1)):
+        net.counts[v] = net.counts.get(v, 0) + n
+    if lean_expected(variant, net.precision, e, io, k_split):
+        net.counts['lean_epilogue'] = 1
+    net.names = [n for n in ('src', 'shortcut', 'out', 'out2', 'after', 'after2') if n in net.tid]
+    return net
+
+
+def _seed(*key):
+    import zlib
+    return zlib.crc32(repr(key).encode())
+
+
+def epilogue_net(precision, case, variant, epi, io='f32'):
+    """selector (3 -> C) -> 'src'; a 3x3 selector -> 'shortcut' (32 channels wider than cout, halo 2); the conv of CONV_CASES[case]
+    with EPILOGUES[epi], pinned to `variant` -> 'out' (halo 1; a slice of a tensor a 3x3 selector has written where the epilogue or
+    the case says so) and 'out2'; sink convs 'after' / 'after2' read both with their halos.  The weights depend on (case, epi) alone:
+    every variant, io and precision of a case computes the same numbers."""
+    c = CONV_CASES[case]
+    return _stage(Net(precision), np.random.default_rng(_seed('epilogue', case, epi)), c, EPILOGUES[epi], variant, io, stride=c.get('stride', 1))
+
+
+UP2_CASES = ('c64_3x3', 'c128_3x3')
+UP2_EPILOGUES = {'relu_res0': dict(relu=True, res=0), 'res32': dict(res=32), 'res32_out2': dict(res=32, out2=0)}
+
+
+def up2_net(precision, case, variant, epi, io='f32'):
+    """As epilogue_net, but 'shortcut' comes from a STRIDE-2 3x3 selector on the same frames -- ceil(h / 2) x ceil(w / 2) -- and the
+    conv under test reads it at (y >> 1, x >> 1) (RetinaFace's FPN merge, pack/retinaface.py)."""
+    return _stage(Net(precision), np.random.default_rng(_seed('up2', case, epi)), CONV_CASES[case], UP2_EPILOGUES[epi], variant, io, res_up2=1)
+
+
+def up2_programs(case, variant, precision):
+    c = CONV_CASES[case]
+    out = []
+    for epi in UP2_EPILOGUES:
+        sizes = tuple(s for s in case_sizes(case) if variant_eligible(variant, precision, cout=c['cout'], k=c['k'], size=s, cin=c['C']))
+        out += [(epi, io, sizes) for io in ('f32', 'split') if sizes and not (io == 'split' and (precision == 'f32' or variant == 'generic'))]
+    return out
+
+
+KSPLIT_CASES = {'c256_3x3': dict(C=256, cout=128, k=3), 'c512_1x1': dict(C=512, cout=128, k=1)}
+KSPLIT_EPILOGUES = {'relu': dict(relu=True), 'prelu': dict(prelu=True), 'res32': dict(res=32), 'res0_out2_slice': dict(res=0, out2=32),
+                    'affine_prelu': dict(prelu=True, affine=True)}                  # in_affine: 3x3 only, no second output (Program.conv)
+KSPLIT_VARIANTS = ('split_2x2', 'split_2x4', 'split_1x4')                            # the 3-stage split-role kernels know K ranges
+KSPLITS = (2, 4)
+
+
+def ksplit_net(precision, case, variant, epi, k_split, io='f32'):
+    """As epilogue_net with K cut in `k_split` ranges: the kernels write raw partial sums, splitk_reduce_kernel runs the whole epilogue.
+    Every output channel has a weight in every range."""
+    return _stage(Net(precision), np.random.default_rng(_seed('ksplit', case, epi, k_split)), KSPLIT_CASES[case], KSPLIT_EPILOGUES[epi],
+                  variant, io, k_split=k_split, nz=4)
+
+
+def ksplit_programs(case, precision):
+    """[(epilogue, k_split, io)] of KSPLIT_CASES[case]."""
+    k = KSPLIT_CASES[case]['k']
+    return [(epi, ks, io) for epi, e in KSPLIT_EPILOGUES.items() if k == 3 or not e.get('affine') for ks in KSPLITS
+            for io in (('f32',) if precision == 'f32' else ('f32', 'split'))]
 
 
 # ---- the cases of tests/test_gpu_layers_exact.py (tests/test_exact_programs_cpu.py walks the same lists) ---------------------------

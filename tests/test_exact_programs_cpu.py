@@ -8,7 +8,10 @@
   the three precisions (a later packer change must not quietly turn these into float32-only tests), gives both sides of every
   pool and copy one exponent, and keeps every tensor of the half-float mode inside the half-float range: a TA_E_RANGE on the
   GPU would be a mistake of the test, not a finding;
-- the loader's program check accepts every program.
+- the loader's program check accepts every program;
+- the conv output-stage programs of tests/test_gpu_conv_exact.py (epilogue_net, up2_net, ksplit_net): reference == torch, the
+  exactness rule through the whole chain, data on which one wrong offset / slope / class / K range / shift changes the answer,
+  the formats each listing assumes, and a per-channel un-scale that is not one value throughout.
 """
 import numpy as np
 import pytest
@@ -30,9 +33,27 @@ def torch_replay(net, fr):
     for op, src, dst, a in net.steps:
         x = t[src]
         if op == 'conv':
-            y = F.conv2d(x[:, :a['W'].shape[1]], T(a['W']), T(a['b']), stride=a['stride'], padding=a['pad'])
-            y = F.relu(y) if a['relu'] else y
+            cout, cin = a['W'].shape[:2]
+            xin = x[:, a['in_ch_off']:a['in_ch_off'] + cin * a['groups']]
+            if a['in_affine'] is not None:                             # the affine first, the zero padding after it
+                xin = xin * T(a['in_affine'][0])[None, :, None, None] + T(a['in_affine'][1])[None, :, None, None]
+            y = F.conv2d(xin, T(a['W']), T(a['b']), stride=a['stride'], padding=a['pad'], groups=a['groups'])
+            y = F.prelu(y, T(a['prelu'])) if a['prelu'] is not None else (F.relu(y) if a['relu'] else y)
             y = F.max_pool2d(y, 2, 2) if a['pool'] else y
+            if a['res'] is not None:
+                r = t[a['res']][:, a['res_ch_off']:a['res_ch_off'] + cout]
+                if a['res_up2']:
+                    r = F.interpolate(r, scale_factor=2, mode='nearest')[:, :, :y.shape[2], :y.shape[3]]
+                y = y + r
+            if a['out2'] is not None:
+                z = y * T(a['scale2'])[None, :, None, None] + T(a['shift2'])[None, :, None, None]
+                full = t[a['out2']].clone() if a['out2'] in t else torch.zeros((y.shape[0], net.P.tensors[net.tid[a['out2']]][0]) + y.shape[2:], dtype=torch.float64)
+                full[:, a['out2_ch_off']:a['out2_ch_off'] + cout] = z
+                t[a['out2']] = full
+            if dst in t or cout != net.P.tensors[net.tid[dst]][0]:
+                full = t[dst].clone() if dst in t else torch.zeros((y.shape[0], net.P.tensors[net.tid[dst]][0]) + y.shape[2:], dtype=torch.float64)
+                full[:, a['out_ch_off']:a['out_ch_off'] + cout] = y
+                y = full
         elif op == 'dwconv':
             C = a['W'].shape[0]
             y = F.conv2d(x[:, :C], T(a['W']), T(a['b']), stride=a['stride'], padding=1, groups=C)
@@ -58,10 +79,12 @@ def torch_replay(net, fr):
 
 
 def check(net, shapes, n=2, seed=100):
-    """Reference == torch on every shape, and what the half-float mode stores stays in its range.  -> the last reference."""
+    """Reference == torch on every shape, and what the half-float mode stores stays in its range.  -> the last reference.
+    A shape is (h, w) of `n` frames, or (n, h, w)."""
     lib.check_program(net.P)                                       # packs the program: net.P.scales / mid_scales exist from here on
-    for h, w in shapes:
-        fr = ep.frames(seed + h * 31 + w, n, h, w)
+    for shape in shapes:
+        h, w = shape[-2:]
+        fr = ep.frames(seed + h * 31 + w, shape[0] if len(shape) == 3 else n, h, w)
         ref = ep.reference(net, fr)
         want = torch_replay(net, fr)
         assert set(ref) == set(want)
@@ -103,10 +126,10 @@ def test_dwconv_programs(precision, C):
     assert all(np.all(net.P.tensor_scales()[net.tid[k]] == 0) for k in names)        # plain depthwise tensors are stored unscaled
 
 
-def _needs_lo(v):
+def _needs_lo(v, bits=11):
     """Some value has more than the 11 bits of a half float's hi word (so more than the 8 of a bf16's as well)."""
     v = np.abs(v[v != 0]).astype(np.int64)
-    return bool(np.any(v // (v & -v) >= 2048))
+    return bool(np.any(v // (v & -v) >= 1 << bits))
 
 
 @pytest.mark.parametrize('precision', ep.PRECISIONS)
@@ -231,3 +254,130 @@ def test_the_reference_refuses_what_is_not_exact():
     net.conv('big', 'bigger', np.full((32, 32, 1, 1), 8.0), np.zeros(32))             # ... but now it is read (and 'bigger' passes 2^24)
     with pytest.raises(AssertionError, match='not exact'):
         ep.reference(net, fr)
+
+
+# ---- the conv output stage: the programs of tests/test_gpu_conv_exact.py -----------------------------------------------------------
+def stage_programs():
+    """(id, builder(precision, variant, io), the variants and ios it is listed under per precision, frame sizes, conv stride)."""
+    out = []
+    for case, c in ep.CONV_CASES.items():
+        for epi in c['epi']:
+            listed = {p: [(v, io) for v in ep.VARIANTS for e_, io, _ in ep.conv_programs(case, v, p) if e_ == epi] for p in ep.PRECISIONS}
+            sizes = ep.case_sizes(case, ep.EPILOGUES[epi].get('affine'))
+            out.append(('epilogue-%s-%s' % (case, epi), lambda p, v, io, case=case, epi=epi: ep.epilogue_net(p, case, v, epi, io),
+                        listed, sizes, c.get('stride', 1)))
+    for case in ep.UP2_CASES:
+        for epi in ep.UP2_EPILOGUES:
+            listed = {p: [(v, io) for v in ep.VARIANTS for e_, io, _ in ep.up2_programs(case, v, p) if e_ == epi] for p in ep.PRECISIONS}
+            out.append(('up2-%s-%s' % (case, epi), lambda p, v, io, case=case, epi=epi: ep.up2_net(p, case, v, epi, io), listed, ep.case_sizes(case), 1))
+    for case in ep.KSPLIT_CASES:
+        for epi, ks, _ in ep.ksplit_programs(case, 'f32'):
+            listed = {p: [(v, io) for v in ep.KSPLIT_VARIANTS for e_, k_, io in ep.ksplit_programs(case, p) if (e_, k_) == (epi, ks)]
+                      for p in ep.PRECISIONS}
+            sizes = ep.KSPLIT_SIZES + ((ep.AFFINE_SIZE,) if ep.KSPLIT_EPILOGUES[epi].get('affine') else ())
+            out.append(('ksplit%d-%s-%s' % (ks, case, epi), lambda p, v, io, case=case, epi=epi, ks=ks: ep.ksplit_net(p, case, v, epi, ks, io),
+                        listed, sizes, 1))
+    return out
+
+
+STAGE = stage_programs()
+_stage_refs = {}
+
+
+def stage_refs(i):
+    """The references of STAGE[i] at every size, from its strictest listing: nothing pinned to float32 where a listing leaves it so
+    (every limit is then 16 bits), held against torch."""
+    if i not in _stage_refs:
+        name, build, listed, sizes, stride = STAGE[i]
+        v, io = listed['bf16x3'][-1]
+        net = build('bf16x3', v, io)
+        refs = []
+        for size in sizes:
+            fr = ep.frames(ep.frame_seed(size), *ep.frame_size(size, stride))
+            ref, want = ep.reference(net, fr), torch_replay(net, fr)
+            assert set(ref) == set(want) >= set(net.names)
+            for k in ref:
+                assert ref[k].shape == want[k].shape and np.array_equal(ref[k], want[k]), (name, k, size)
+            assert (ref['out'].shape[0],) + ref['out'].shape[2:] == tuple(size)
+            refs.append((fr, ref))
+        _stage_refs[i] = (net, refs)
+    return _stage_refs[i]
+
+
+@pytest.mark.parametrize('i', range(len(STAGE)), ids=[s[0] for s in STAGE])
+def test_conv_stage_reference_equals_torch_and_is_exact(i):
+    """float64 reference == torch float64 conv2d / prelu / nearest x2 / slicing at every listed size; `reference` asserts the
+    exactness rule through the whole chain on the way.  The stage does something: ReLU / PReLU meet negative sums, the shortcut and
+    both outputs use more bits than one hi word holds."""
+    net, refs = stage_refs(i)
+    a = [s for s in net.steps if s[1] == 'src' and s[2] == 'out'][0][3]
+    big = max(refs, key=lambda r: r[1]['out'][:, 0].size)[1]               # the 3 x 9 x 10 map
+    assert _needs_lo(big['out']) and _needs_lo(big['src'], 8)          # ('src' stays below 2^11: the sink convs read 'out', which does not)
+    if a['prelu'] is not None:
+        assert len(set(a['prelu'].tolist())) == 5
+    if a['relu']:
+        assert (big['out'] == 0).any()
+    if a['res'] is not None:
+        sc = big['shortcut']
+        assert all(len(np.unique(sc[0, c])) > 1 for c in range(sc.shape[1])) or sc[0, 0].size == 1     # not constant across the map
+
+
+@pytest.mark.parametrize('i', range(len(STAGE)), ids=[s[0] for s in STAGE])
+def test_conv_stage_data_discriminates(i):
+    """A reference with one deliberate mistake differs from the true one at every size where the feature is reachable: a green GPU
+    run cannot come from a shortcut that happened to be constant, slopes that happened to be equal, a shift of zero, ..."""
+    net, refs = stage_refs(i)
+    a = [s for s in net.steps if s[1] == 'src' and s[2] == 'out'][0][3]
+    has = {'up2_unshifted': bool(a['res_up2']), 'res_ch_off+4': a['res'] is not None, 'out2_ch_off+8': a['out2'] is not None,
+           'prelu_shifted': a['prelu'] is not None, 'corner_as_edge': a['in_affine'] is not None, 'k_range_dropped': a['k_split'] > 1,
+           'no_shift2': a['out2'] is not None}
+    assert set(has) == set(ep.MISTAKES)
+    for fr, ref in refs:
+        for mistake in ep.MISTAKES:
+            reachable = has[mistake] and not (mistake == 'up2_unshifted' and ref['out'].shape[2:] == (1, 1))
+            if not reachable:
+                continue
+            wrong = ep.reference(net, fr, mistake=mistake)
+            assert any(not np.array_equal(wrong[k], ref[k]) for k in ('out', 'out2') if k in ref), (mistake, fr.shape)
+        if a['in_affine'] is not None:                                  # the packer's folded form means the same
+            folded = ep.reference(net, fr, mistake='fold')
+            assert all(np.array_equal(folded[k], ref[k]) for k in ref), fr.shape
+    if a['in_affine'] is not None:
+        Wf, b16 = pack.fold_input_affine(a['W'], a['b'], *a['in_affine'])
+        assert np.array_equal(Wf, np.rint(Wf)) and np.array_equal(b16, np.rint(b16)) and len(np.unique(b16, axis=0)) == 16
+
+
+@pytest.mark.parametrize('precision', ep.PRECISIONS)
+@pytest.mark.parametrize('i', range(len(STAGE)), ids=[s[0] for s in STAGE])
+def test_conv_stage_programs_load_as_listed(i, precision):
+    """Every (variant, io) a program is listed under: the loader's check accepts it, its tensors have the formats the listing assumes
+    (so the pinned kernel is eligible and the lean drain is where lean_expected says), the half-float mode stays inside its range, and
+    the per-channel un-scale of the conv under test is not one value throughout."""
+    name, build, listed, sizes, stride = STAGE[i]
+    _, refs = stage_refs(i)
+    assert listed[precision], name
+    for v, io in listed[precision]:
+        net = build(precision, v, io)
+        lib.check_program(net.P)
+        f = formats(net)
+        oi = net.conv_ops['out']
+        op = net.P.ops[oi]
+        staged = (op['out_ch_off'] | op['res_ch_off'] | op['out2_ch_off']) % 8 == 0
+        assert f['src'] == (pack.FMT_F32 if v == 'generic' or not staged else FMT_OF[precision]), (name, v, io, f)
+        assert v == 'generic' or staged
+        for k in ('shortcut', 'out', 'out2'):
+            if k in f:
+                want = FMT_OF[precision] if io == 'split' and net.P.tensors[net.tid[k]][0] % 32 == 0 else pack.FMT_F32
+                assert f[k] == want, (name, v, io, k, f)
+        if precision != 'f16x3':
+            continue
+        for fr, ref in refs:
+            for k, tid in net.tid.items():
+                if k in ref:
+                    in_half_range(ref[k], net.P.scales[tid], k)
+        cout = op['cout']
+        a_out = net.P._exponents(net.P.scales, op, 'out')[:cout]
+        us = a_out - net.P._fold[oi]['wexp'][:cout]
+        assert len(np.unique(us)) >= 2, (name, v, io)
+        if io == 'split':
+            assert len(np.unique(a_out)) >= 2, (name, v, io, a_out)

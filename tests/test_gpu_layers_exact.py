@@ -16,6 +16,7 @@ import pytest
 
 from terran_amd import pack
 from tests import exact_programs as ep
+from tests.util import run_exact as run, same
 
 pytestmark = pytest.mark.gpu
 
@@ -26,33 +27,6 @@ def ctx():
     c = lib.Context(0)
     yield c
     c.close()
-
-
-def same(got, want, what):
-    """Bit equality with float32(reference); the message names how many values differ and the first of them."""
-    want = np.asarray(want).astype(np.float32)
-    assert got.shape == want.shape, (what, got.shape, want.shape)
-    if not np.array_equal(got, want):
-        bad = np.argwhere(got != want)
-        i = tuple(bad[0])
-        raise AssertionError('%s: %d of %d values differ, first at (n, c, y, x) = %s: got %r, want %r'
-                             % (what, len(bad), got.size, i, float(got[i]), float(want[i])))
-
-
-def run(ctx, net, fr, names, what=''):
-    """One forward of `net` on the frames `fr`; every tensor of `names` must equal the float64 reference.  -> the reference."""
-    from terran_amd import lib
-    m = getattr(net, 'model', None)
-    if m is None:
-        m = net.model = lib.Model(ctx, net.P)
-    ref = ep.reference(net, fr)
-    frames = ctx.upload(fr)
-    m.forward_frames(frames)
-    assert ctx.lib.ta_debug_range_check(ctx.h) == lib.OK, 'a tensor left the half-float range: the test program is wrong'
-    for name in names:
-        same(m.read(name), ref[name], '%s %s %s' % (what, fr.shape, name))
-    frames.free()
-    return ref
 
 
 # ---- preprocess -----------------------------------------------------------------------------------------------------------------

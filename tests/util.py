@@ -233,3 +233,34 @@ def two_conv_program(precision='f32', pad2=0, mid_halo=1, c=32, **second):
     P.conv(t1, t2, rng.normal(0, 0.1, (c, c, 3, 3)).astype(np.float32), rng.normal(0, 0.1, c).astype(np.float32), pad=pad2, **second)
     P.outputs = [t2]
     return P
+
+
+# ---- the programs of tests/exact_programs.py on the GPU: bit equality with their float64 reference --------------------------------
+def same(got, want, what):
+    """Bit equality with float32(reference); the message names how many values differ and the first of them."""
+    want = np.asarray(want).astype(np.float32)
+    assert got.shape == want.shape, (what, got.shape, want.shape)
+    if not np.array_equal(got, want):
+        bad = np.argwhere(got != want)
+        i = tuple(bad[0])
+        raise AssertionError('%s: %d of %d values differ, first at (n, c, y, x) = %s: got %r, want %r'
+                             % (what, len(bad), got.size, i, float(got[i]), float(want[i])))
+
+
+def run_exact(ctx, net, fr, names, what='', ref=None):
+    """One forward of `net` on the frames `fr`; every tensor of `names` must equal the float64 reference (`ref`: one computed before
+    for the same ops and frames).  -> the reference."""
+    from terran_amd import lib
+    from tests import exact_programs as ep
+    m = getattr(net, 'model', None)
+    if m is None:
+        m = net.model = lib.Model(ctx, net.P)
+    if ref is None:
+        ref = ep.reference(net, fr)
+    frames = ctx.upload(fr)
+    m.forward_frames(frames)
+    assert ctx.lib.ta_debug_range_check(ctx.h) == lib.OK, 'a tensor left the half-float range: the test program is wrong'
+    for name in names:
+        same(m.read(name), ref[name], '%s %s %s' % (what, fr.shape, name))
+    frames.free()
+    return ref
