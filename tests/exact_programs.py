@@ -13,6 +13,21 @@ bound is taken over sum |w| |x| + |b|, so it holds for every summation order a k
 it is carried on: times max(1, |slope|) of an integer PReLU slope, plus |shortcut|, and times |scale2| plus |shift2| (integers)
 into the second output, each against the limit of the tensor it lands in.
 
+The tolerance modes (TOLERANCE_MODES: 'f16', 'f16x2', 'bf16') drop words on purpose, so their rule is per mode and per storage
+format, and `reference` asserts it per tensor from the packed program's tensor_formats(), scales and weight-row exponents (class
+Rounding: each limit is the format's own rounding function, and a value obeys the rule when that function leaves it unchanged):
+- a TA_FMT_F16 tensor holds one IEEE half per value: 11 significant bits (10 stored + the implicit one) at the channel's exponent,
+  |x 2^a| <= 65504; TA_FMT_SPLIT16 holds hi + lo halves: 22 bits in the same range; TA_FMT_SPLIT two bf16 words: 16 bits; float32: 24;
+- 'f16' reads 11 bits of either operand (the hi half of a weight row, a TA_FMT_F16 tensor as it is, a float32 one rounded in registers);
+- 'f16x2' computes (w_hi + w_lo) * x_hi: the activations a conv reads have 11 bits (x_lo = 0), the weights may use the whole pair;
+- 'bf16' computes hi * hi on bf16 words: 8 significant bits per operand;
+- every partial sum (sum |w| |x| + |b|) stays below 2^24, the float32 accumulator's integers.
+Programs of family 'exact' obey all of this, so no rounding changes a value and the reference equals plain float64 arithmetic.
+Programs of family 'rounded' break a bit count on purpose; `reference` then applies the one rounding the mode defines -- to nearest
+even when an operand is formed or a tensor is stored -- in float64, exactly (products and sums still stay exact below 2^24).
+The sink convs of an 'f16x2' / 'bf16' program run in the sister mode that reads both words ('f16x3' / 'bf16x3'), so what the conv under
+test stores may use its whole format; 'f16' has no such sister for a TA_FMT_F16 tensor, whose 11 bits every reader gets anyway.
+
 Every program is of kind MODEL_RETINAFACE unless said otherwise: its preprocess writes BGR integers 0..255 as float32, 4th
 channel 0, into the tensor named 'input'.  A SELECTOR conv (1x1 or 3x3, integer weights and bias) turns that into an exactly
 known C-channel tensor in whatever format the packer picks; the ops under test read it.
@@ -121,13 +136,105 @@ def _exact(what, bound, limit):
     assert top < limit, '%s: partial sums reach %.0f, not exact below %d' % (what, top, limit)
 
 
+
+# ---- the roundings of the tolerance modes, in float64 ---------------------------------------------------------------------------
+TOLERANCE_MODES = ('f16', 'f16x2', 'bf16')
+SISTER_MODE = {'f16': 'f16', 'f16x2': 'f16x3', 'bf16': 'bf16x3'}     # reads both words of what the mode stores
+HALF = dict(bits=11, emin=-24, top=F16_MAX)      # IEEE half: 10 stored bits + the implicit one, subnormal quantum 2^-24, ends at 65504
+BF16 = dict(bits=8, emin=-133, top=np.inf)       # bfloat16: 7 stored bits + the implicit one, float32's exponents
+
+
+def rne(v, bits, emin, top, toward_zero=False):
+    """float64 `v` rounded to `bits` significant bits, to nearest even (or toward zero), quantum never below 2^emin."""
+    v = np.asarray(v, np.float64)
+    _, e = np.frexp(v)                                             # |v| in [2^(e - 1), 2^e)
+    q = np.maximum(e - bits, emin)
+    t = np.ldexp(v, -q)
+    r = np.ldexp(np.trunc(t) if toward_zero else np.rint(t), q)    # np.rint: halves to even
+    assert not r.size or np.abs(r).max() <= top, 'a value leaves the range of its format (%g)' % np.abs(r).max()
+    return r
+
+
+def pair(v, word):
+    """hi + lo of two `word`-format words: hi = rne(v), lo = rne(v - hi)."""
+    hi = rne(v, **word)
+    return hi + rne(v - hi, **word)
+
+
+class Rounding:
+    """What a packed tolerance-mode program rounds where.  Everything is per channel in STORED units (value times 2^a[c], the
+    packer's exponents) and comes back in real units.  `changed` collects (tensor or op, what) wherever a rounding was not the identity."""
+
+    def __init__(self, net, mistake=None):
+        from terran_amd.pack import FMT_F16, FMT_F32, FMT_SPLIT, FMT_SPLIT16
+        P = net.P
+        P.blob()                                                   # settles formats, exponents and the weight-row exponents
+        self.net, self.mistake, self.changed = net, mistake, set()
+        self.half = dict(HALF, top=np.inf) if mistake else HALF        # (a wrong reference may leave the range)
+        self.fmt = {n: P.tensor_formats()[t] for n, t in net.tid.items()}
+        self.a = {n: P.scales[t].astype(np.int32) for n, t in net.tid.items()}
+        self.F16, self.F32, self.SPLIT, self.SPLIT16 = FMT_F16, FMT_F32, FMT_SPLIT, FMT_SPLIT16
+
+    def _note(self, got, want, key):
+        if not np.array_equal(got, want):
+            self.changed.add(key)
+        return got
+
+    def store(self, name, y, ch_off=0):
+        """y (N, c, H, W) real values written into channels ch_off.. of tensor `name` -> what a reader of every word gets back."""
+        a = self.a[name][ch_off:ch_off + y.shape[1]][None, :, None, None]
+        s, f = np.ldexp(y, a), self.fmt[name]
+        if f == self.F16:
+            r = rne(s, toward_zero=self.mistake == 'store_truncated', **self.half)
+        elif f == self.SPLIT16:
+            r = pair(s, self.half)
+        elif f == self.SPLIT:
+            r = pair(s, BF16)
+        else:
+            r = s.astype(np.float32).astype(np.float64)
+        # the range guard of a program with half-float convs watches every store, float32 ones included (conv_common.h: ta_range_report)
+        assert self.mistake or self.net.precision == 'bf16' or not r.size or np.abs(r).max() <= F16_MAX, '%s: %g leaves the half-float range' % (name, np.abs(r).max())
+        return self._note(np.ldexp(r, -a), y, (name, 'store'))
+
+    def read(self, name, x, mode):
+        """The activation operand a conv of arithmetic mode `mode` forms from tensor `name` (x: all its channels, real values)."""
+        a = self.a[name][None, :, None, None]
+        s = np.ldexp(x, a)
+        if mode in ('f16', 'f16x2') and not (mode == 'f16x2' and self.mistake == 'x_lo_kept'):
+            s = rne(s, **self.half)            # the hi half of a pair, a TA_FMT_F16 value itself, or a float32 one rounded in registers
+        elif mode == 'bf16':
+            s = rne(s, **BF16)
+        return self._note(np.ldexp(s, -a), x, (name, 'read by ' + mode))
+
+    def weights(self, a_step, W, src):
+        """The weight operand of the conv of step dict `a_step`: W (cout, cin_g, kh, kw) real -> what the mode multiplies with, real.
+        Rows are packed times 2^(wexp[co] - a_in[c]) (pack/layout.py: split_f16_rows, split_bf16_rows; program.py: rows64)."""
+        mode, g = a_step['precision'], a_step['groups']
+        cout, cin = W.shape[:2]
+        wexp = np.asarray(self.net.P._fold[a_step['op']]['wexp'][:cout], np.int32)
+        a_in = self.a[src][a_step['in_ch_off']:a_step['in_ch_off'] + cin * g].reshape(g, cin)
+        e = wexp[:, None] - np.repeat(a_in, cout // g, axis=0)                       # (cout, cin)
+        s = np.ldexp(W, e[:, :, None, None])
+        word = self.half if mode in ('f16', 'f16x2', 'f16x3') else BF16
+        if mode in ('f16', 'bf16') or (mode == 'f16x2' and self.mistake == 'w_lo_dropped'):
+            r = rne(s, **word)
+        elif mode == 'f32':
+            r = s
+        else:
+            r = pair(s, word)
+        return self._note(np.ldexp(r, -e[:, :, None, None]), W, (a_step['op'], 'weights'))
+
+
 # ---- programs -------------------------------------------------------------------------------------------------------------------
 class Net:
     """A pack.Program plus the recipe `reference` replays in float64.  Tensors are addressed by name."""
 
-    def __init__(self, precision, kind=pack.MODEL_RETINAFACE, in_halo=1, shape_only_input=False):
+    def __init__(self, precision, kind=pack.MODEL_RETINAFACE, in_halo=1, shape_only_input=False, pixel_shift=0, family='exact'):
         self.P = P = pack.Program(kind, precision)
         self.precision = precision
+        self.pixel_shift = pixel_shift                            # the frames are `frames(...) >> pixel_shift`: 0 .. 255 >> shift
+        self.quantum = LO_QUANTUM if precision == 'f16x2' else 0      # every value is an integer times 2^quantum
+        self.family = family                                      # 'exact': no rounding changes a value; 'rounded': one does (module text)
         self.tid = {}
         self.steps = []
         self.mid_ops = {}                                         # dst name -> op index of a dw+pw block
@@ -135,7 +242,8 @@ class Net:
         t0 = P.tensor(4, in_halo, alias_of=-2 if shape_only_input else -1, name='input')
         self.tid['input'] = t0
         P.input_tensor = t0
-        P.input_stats = PIXEL_STATS
+        top = 256 >> pixel_shift                                  # moments of uniform 0 .. top - 1
+        P.input_stats = (np.array([(top - 1) / 2.0] * 3 + [0.0]), np.array([(top * top - 1.0) / 12.0] * 3 + [0.0]))
 
     def tensor(self, name, c, halo=0, f32=False):
         self.tid[name] = self.P.tensor(c, halo, name=name, f32=f32)
@@ -143,18 +251,19 @@ class Net:
 
     def conv(self, src, dst, W, b, *, stride=1, pad=None, relu=False, pool=False, prelu=None, res=None, res_ch_off=0, res_up2=0,
              out2=None, out2_ch_off=0, scale2=None, shift2=None, out_ch_off=0, in_ch_off=0, cin_p=None, groups=1, k_split=0,
-             in_affine=None, variant=0):
-        """pack.Program.conv with tensors by name.  The output stage in the kernels' order: conv + bias (in_affine: of scale * x +
+             in_affine=None, variant=0, precision=None):
+        """pack.Program.conv with tensors by name (`precision`: this op alone runs in another arithmetic mode).
+        The output stage in the kernels' order: conv + bias (in_affine: of scale * x +
         shift, zero-padded AFTER the affine), ReLU / PReLU, + res[:, res_ch_off:+cout, y >> res_up2, x >> res_up2], store into the
         slice at out_ch_off, then out2[:, out2_ch_off:+cout] = out * scale2 + shift2."""
         act = pack.ACT_PRELU if prelu is not None else (pack.ACT_RELU if relu else pack.ACT_NONE)
         tid = lambda n: -1 if n is None else self.tid[n]
-        self.conv_ops[dst] = len(self.P.ops)
+        self.conv_ops[dst] = oi = len(self.P.ops)
         self.P.conv(self.tid[src], self.tid[dst], W, b, stride=stride, pad=pad, act=act, pool=pool, prelu=prelu, res=tid(res),
                     res_ch_off=res_ch_off, res_up2=res_up2, out2=tid(out2), out2_ch_off=out2_ch_off, scale2=scale2, shift2=shift2,
                     out_ch_off=out_ch_off, in_ch_off=in_ch_off, cin_p=cin_p, groups=groups, k_split=k_split, in_affine=in_affine,
-                    variant=variant)
-        self.steps.append(('conv', src, dst, dict(W=W, b=b, stride=stride, pad=W.shape[2] // 2 if pad is None else pad, relu=relu, pool=pool,
+                    variant=variant, precision=precision)
+        self.steps.append(('conv', src, dst, dict(op=oi, src=src, precision=precision or self.precision, W=W, b=b, stride=stride, pad=W.shape[2] // 2 if pad is None else pad, relu=relu, pool=pool,
                                                   prelu=prelu, res=res, res_ch_off=res_ch_off, res_up2=res_up2, out2=out2,
                                                   out2_ch_off=out2_ch_off, scale2=scale2, shift2=shift2, out_ch_off=out_ch_off,
                                                   in_ch_off=in_ch_off, groups=groups, k_split=k_split, in_affine=in_affine)))
@@ -196,6 +305,7 @@ class Net:
         return LIMIT_F32 if self.tid[name] in self.P.f32_only and not self.read_by_an_op(name) else LIMIT_SPLIT
 
 
+MODE_MISTAKES = ('x_lo_kept', 'w_lo_dropped', 'store_truncated', 'slab64_second_half_swapped')     # of the tolerance modes
 MISTAKES = ('up2_unshifted', 'res_ch_off+4', 'out2_ch_off+8', 'prelu_shifted', 'corner_as_edge', 'k_range_dropped', 'no_shift2')
 
 
@@ -216,22 +326,32 @@ def k_range_mask(W, k_split, r):
     return m.reshape(kh, kw, cin).transpose(2, 0, 1)[None]
 
 
-def _conv_step(net, ref, x, dst, a, lim, chans, mistake):
+def _conv_step(net, ref, x, dst, a, lim, chans, mistake, R=None):
     """One conv of `reference` with its whole output stage.  Returns what `dst` holds afterwards; writes `out2` into ref itself.
     `mistake`: one of MISTAKES (the deliberately wrong references of tests/test_exact_programs_cpu.py), or 'fold': in_affine by the
     packer's folded weights and border-class biases instead of by its meaning."""
     strict = mistake is None
     W, b, g = np.asarray(a['W'], np.float64), np.asarray(a['b'], np.float64), a['groups']
     cout, cin = W.shape[:2]
+    lim2 = net.limit(a['out2']) if a['out2'] is not None and R is None else np.ldexp(LIMIT_F32, net.quantum)
+    wq = (lambda w: R.weights(a, w, a['src'])) if R else (lambda w: w)     # a tolerance mode: the operands as the mode forms them
+    if R:
+        x = R.read(a['src'], x, a['precision'])
+        if mistake == 'slab64_second_half_swapped' and dst == 'out' and R.fmt[a['src']] == R.F16:
+            W = W.copy()                                                    # tap (0, 0): the 32-channel halves of every 64-channel slab
+            W[:, :, 0, 0] = W[:, :, 0, 0].reshape(cout, cin // 64, 2, 32)[:, :, ::-1].reshape(cout, cin)
     xin = x[:, a['in_ch_off']:a['in_ch_off'] + cin * g]
     assert xin.shape[1] == cin * g
     xabs = np.abs(xin)
     if a['k_split'] > 1 and mistake == 'k_range_dropped':
         W = W * ~k_range_mask(W, a['k_split'], 1)
     aff = a['in_affine']
-    if aff is not None and mistake in ('fold', 'corner_as_edge'):
+    if aff is not None and (mistake in ('fold', 'corner_as_edge') or R):      # (a tolerance mode rounds the FOLDED weights)
         Wf, b16 = pack.fold_input_affine(W, b, *aff)
-        y = conv_ref(xin, Wf, np.zeros(cout), 1, 1)
+        if strict:
+            sc, sh = (np.asarray(v, np.float64)[None, :, None, None] for v in aff)
+            _exact(dst, conv_ref(xabs * np.abs(sc) + np.abs(sh), np.abs(W), np.abs(b), 1, 1), lim)
+        y = conv_ref(xin, wq(Wf), np.zeros(cout), 1, 1)
         cy, cx = border_class(y.shape[2]), border_class(y.shape[3])
         cls = 4 * cy[:, None] + cx[None, :]
         if mistake == 'corner_as_edge':
@@ -242,8 +362,8 @@ def _conv_step(net, ref, x, dst, a, lim, chans, mistake):
         sc, sh = (np.asarray(v, np.float64)[None, :, None, None] for v in aff)
         xin, xabs = xin * sc + sh, xabs * np.abs(sc) + np.abs(sh)                       # bounds the folded form as well
     if aff is not None or a['in_affine'] is None:
-        cg, og = cin, cout // g
-        y = np.concatenate([conv_ref(xin[:, i * cg:(i + 1) * cg], W[i * og:(i + 1) * og], b[i * og:(i + 1) * og], a['stride'], a['pad'])
+        cg, og, Wq = cin, cout // g, wq(W)
+        y = np.concatenate([conv_ref(xin[:, i * cg:(i + 1) * cg], Wq[i * og:(i + 1) * og], b[i * og:(i + 1) * og], a['stride'], a['pad'])
                             for i in range(g)], axis=1)
     cg, og = cin, cout // g
     bound = np.concatenate([conv_ref(xabs[:, i * cg:(i + 1) * cg], np.abs(W[i * og:(i + 1) * og]), np.abs(b[i * og:(i + 1) * og]),
@@ -279,12 +399,16 @@ def _conv_step(net, ref, x, dst, a, lim, chans, mistake):
         s2, h2 = (np.asarray(v, np.float64)[None, :, None, None] for v in (a['scale2'], a['shift2']))
         z = y * s2 + (0.0 if mistake == 'no_shift2' else h2)
         if strict:
-            _exact(a['out2'], bound * np.abs(s2) + np.abs(h2), net.limit(a['out2']))
-            assert np.array_equal(z, np.rint(z)), a['out2']
+            _exact(a['out2'], bound * np.abs(s2) + np.abs(h2), lim2)
+            assert np.array_equal(np.ldexp(z, -net.quantum), np.rint(np.ldexp(z, -net.quantum))), a['out2']
+        if R:
+            z = R.store(a['out2'], z, a['out2_ch_off'])
         off = a['out2_ch_off'] + (8 if mistake == 'out2_ch_off+8' else 0)
         full = ref[a['out2']].copy() if a['out2'] in ref else np.zeros((y.shape[0], chans[a['out2']]) + y.shape[2:])
         full[:, (off + np.arange(cout)) % full.shape[1]] = z
         ref[a['out2']] = full
+    if R:
+        y = R.store(dst, y, a['out_ch_off'])
     if a['out_ch_off'] or cout != chans[dst]:                       # into a slice: every other channel stays what its producer wrote
         full = ref[dst].copy() if dst in ref else np.zeros((y.shape[0], chans[dst]) + y.shape[2:])
         assert full.shape[2:] == y.shape[2:], (dst, full.shape, y.shape)
@@ -296,14 +420,19 @@ def _conv_step(net, ref, x, dst, a, lim, chans, mistake):
 def reference(net, fr, mistake=None):
     """float64 value of every named tensor of `net` for the uint8 RGB frames `fr`, as (N, C, H, W).  Asserts the exactness rule
     of the module text on every step.  A dw+pw block also yields '<dst>:mid', its depthwise intermediate.  `mistake`: see
-    _conv_step (the rule is then not asserted: a wrong reference may break it)."""
+    _conv_step (the rule is then not asserted: a wrong reference may break it).  A program of a tolerance mode is packed here (its
+    exponents decide where a half float rounds); net.rounding.changed then says which roundings were not the identity."""
     ref = {'input': input_ref(fr)}
+    assert fr.max() < 256 >> net.pixel_shift, 'the frames of this program are frames(...) >> %d' % net.pixel_shift
     chans = {n: net.P.tensors[t][0] for n, t in net.tid.items()}
+    R = net.rounding = Rounding(net, mistake) if net.precision in TOLERANCE_MODES else None
     for op, src, dst, a in net.steps:
         x = ref[src]
-        lim = net.limit(dst)
+        lim = net.limit(dst) if R is None else np.ldexp(LIMIT_F32, net.quantum)      # 2^24 quanta: the float32 accumulator's integers
         if op == 'conv':
-            y = _conv_step(net, ref, x, dst, a, lim, chans, mistake)
+            y = _conv_step(net, ref, x, dst, a, lim, chans, mistake, R)
+            if R and mistake is None and net.family == 'exact':
+                assert not R.changed, "%s: the exactness rule of mode '%s' does not hold: %s" % (dst, net.precision, sorted(map(str, R.changed)))
         elif op == 'dwconv':
             y = dw_ref(x, a['W'], a['b'], a['stride'])
             _exact(dst, dw_ref(np.abs(x), np.abs(a['W']), np.abs(a['b']), a['stride']), lim)
@@ -333,7 +462,8 @@ def reference(net, fr, mistake=None):
         else:
             raise AssertionError(op)
         if mistake is None:
-            assert np.array_equal(y, np.rint(y)), dst               # integers: below the limit they have their bits
+            yq = np.ldexp(y, -net.quantum)
+            assert np.array_equal(yq, np.rint(yq)), dst               # integers (of the net's quantum): below the limit they have their bits
             _exact(dst, np.abs(y), lim)
         assert y.shape[1] == chans[dst], (dst, y.shape, chans[dst])
         ref[dst] = y
@@ -349,15 +479,15 @@ def selector(net, rng, name, C, *, k=1, wmax=64, halo=1, relu=False, f32=False, 
     return name
 
 
-def sink(net, rng, src, name, C, cout=64, variant=0):
+def sink(net, rng, src, name, C, cout=64, variant=0, precision=None, taps=range(9)):
     """`src` (halo 1) -> conv 3x3 pad 1 (C -> cout, one +-1 weight per tap and output) -> `name` (float32).  Its border outputs
     read the halo of `src`: exact only while that halo is still zero.  cout = 64 keeps a 32-channel-block `src` pre-split."""
     net.tensor(name, cout, 0, f32=True)
     W = np.zeros((cout, C, 3, 3))
     for o in range(cout):
-        for t in range(9):
+        for t in taps:                                              # (fewer taps: a sink whose sums must stay small)
             W[o, rng.integers(0, C), t // 3, t % 3] = rng.choice([-1, 1])
-    net.conv(src, name, W, np.zeros(cout), variant=variant)
+    net.conv(src, name, W, np.zeros(cout), variant=variant, precision=precision)
     return name
 
 
@@ -512,8 +642,9 @@ FULL_SIZE_CASES = ('c128_3x3', 'c128to40in192_1x1')   # every kernel's staged an
 AFFINE_SIZE = (1, 6, 1)                        # one column: every pixel is of an 'only' class across and a first / middle / last down
 
 
-def case_sizes(case, affine=False):
-    return (SIZES if case in FULL_SIZE_CASES else THIN_SIZES) + ((AFFINE_SIZE,) if affine else ())
+def case_sizes(case, affine=False, precision='f32'):
+    full = MODE_FULL_SIZE_CASES if precision in ('f16', 'f16x2', 'bf16') else FULL_SIZE_CASES
+    return (SIZES if case in full else THIN_SIZES) + ((AFFINE_SIZE,) if affine else ())
 
 
 def win_patch_rows(h, w, k, BM):
@@ -524,16 +655,19 @@ def win_patch_rows(h, w, k, BM):
 
 
 def variant_eligible(variant, precision, *, cout, k, stride=1, groups=1, staged=True, k_split=0, size=None, cin=64):
-    """csrc/conv_igemm.hip: variant_eligible, for a conv whose input is float32 under 'generic' and in the precision's own format
-    otherwise (cin % 32 == 0, so K is uniform)."""
+    """csrc/conv_igemm.hip: variant_eligible, for a conv whose input is float32 where src_is_f32 says so and in the precision's own
+    format otherwise (cin % 32 == 0, so K is uniform).  'f16': one 64-channel slab already counts as deep, pipe64 reads float32 only
+    (src_is_f32), and a TA_FMT_F16 input takes no groups (pack/storage.py), so no split-role kernel runs a grouped conv."""
     coutp = -(-cout // 32) * 32
-    deep = k * k * cin // 32 >= 2
+    deep = k * k * cin // 32 >= 2 or precision == 'f16'
     if variant == 'generic':
         return groups == 1
     if not (deep and staged):
         return False
     if variant == 'pipe64':
         return coutp % 64 == 0 and groups == 1
+    if precision == 'f16' and (groups > 1 or cin % 64):
+        return False
     if variant in ('split_2x2', 'split_2x4'):
         return coutp % 128 == 0
     if variant == 'split_1x4':
@@ -541,26 +675,53 @@ def variant_eligible(variant, precision, *, cout, k, stride=1, groups=1, staged=
     if variant == 'split_2x2_w2':
         return coutp % 128 == 0 and k_split <= 1
     if variant == 'win_2x2':
-        return (precision == 'f16x3' and stride == 1 and k_split <= 1 and k * k >= 4 and coutp % 128 == 0
+        return (precision in ('f16x3', 'f16x2') and stride == 1 and k_split <= 1 and k * k >= 4 and coutp % 128 == 0
                 and (size is None or win_patch_rows(size[1], size[2], k, 128) <= 384))
     raise AssertionError(variant)
+
+
+def src_is_f32(variant, precision):
+    """The conv under test reads a float32 'src': the generic kernel always, pipe64 in the 'f16' mode."""
+    return variant == 'generic' or (variant == 'pipe64' and precision == 'f16')
+
+
+MODE_PIXEL_SHIFT = {'f16': 5, 'f16x2': 5, 'bf16': 2}
+# The frames of an 'exact' program of a tolerance mode are frames(...) >> shift, so that the bit counts of the module text hold:
+#   'f16'   0 .. 7:  |src| <= 3 * 7 + 8 = 29, |sums| <= 4 * 4 * 29 + 50 = 514, times a PReLU slope of 3 and plus a shortcut of at most
+#           27 * 7 + 8 = 197: 1739, and the second output (2 y + 100) / 2 <= 1789 -- all below 2^11, what a TA_FMT_F16 tensor holds;
+#   'f16x2' 0 .. 7 as well (x_lo = 0); one weight per output channel is 1 + 2^-11 times its magnitude (hi 1, lo 2^-11), so the values
+#           are multiples of 2^-11 below 2^11 (the second output: of 2^-10 below 2^12): the 22 bits of a half-float pair; the sinks
+#           have two taps, opposite corners, so that their float32 sums stay below 2^13 at that quantum;
+#   'bf16'  0 .. 63: |src| <= 3 * 63 + 8 = 197: 8 bits, one bf16 word; the outputs stay far below the 16 bits of a bf16 pair.
+LO_FACTOR = 1.0 + 2.0 ** -11                       # 12 significant bits: hi = 1, lo = 2^-11 (times the row's power of two)
+LO_QUANTUM = -11                                   # ... so an 'f16x2' program holds multiples of 2^-11, exact in float32 below 2^13
+MODE_CONV_CASES = {'c64to64_1x1': dict(C=64, cout=64, k=1, epi=('plain', 'prelu_res32_out2', 'relu_out2'))}      # 'f16': ONE slab of 64
+MODE_FULL_SIZE_CASES = ('c128_3x3',)               # the single pixel and the exact tile: one case per mode
+
+
+def mode_frames(net, size, stride=1):
+    return frames(frame_seed(size), *frame_size(size, stride)) >> net.pixel_shift
+
+
+def all_cases(precision):
+    return dict(CONV_CASES, **MODE_CONV_CASES) if precision in TOLERANCE_MODES else CONV_CASES
 
 
 def conv_programs(case, variant, precision):
     """[(epilogue, io, sizes)] `variant` can run of CONV_CASES[case] in `precision`.  io 'f32': shortcut and outputs pinned to float32
     ('generic': the input as well); 'split': every tensor in the precision's pre-split format, where the split-role and window
     kernels take the lean drain for LEAN_EPILOGUES."""
-    c = CONV_CASES[case]
+    c = all_cases(precision)[case]
     staged = c.get('out_off', 0) % 8 == 0
     out = []
     for epi in c['epi']:
         e = EPILOGUES[epi]
-        sizes = [s for s in case_sizes(case, e.get('affine'))
+        sizes = [s for s in case_sizes(case, e.get('affine'), precision)
                  if variant_eligible(variant, precision, cout=c['cout'], k=c['k'], stride=c.get('stride', 1), groups=c.get('groups', 1),
                                      staged=staged, size=s, cin=c['C'] // c.get('groups', 1))]
         for io in ('f32', 'split'):
-            if io == 'split' and (precision == 'f32' or variant == 'generic'):
-                continue
+            if io == 'split' and (precision == 'f32' or (variant == 'generic' and precision not in TOLERANCE_MODES)):
+                continue                               # (the tolerance modes: the generic kernel's drains store their formats as well)
             if sizes:
                 out.append((epi, io, tuple(sizes)))
     return out
@@ -589,49 +750,104 @@ def lean_expected(variant, precision, e, io, k_split=0):
     return int((variant in SPLIT_VARIANTS or variant.startswith('win')) and precision != 'f32' and io == 'split' and k_split <= 1 and shape)
 
 
-def _stage(net, rng, c, e, variant, io, *, stride=1, res_from=None, res_up2=0, k_split=0, nz=3, seed_affine=True):
-    """'src' -> the conv under test with epilogue `e` -> 'out' (-> 'out2'), and a sink conv behind each output."""
+STAGE_DATA = dict(src_wmax=1, mags=(4, 1, 2, 1), sink_taps=None, scale2=(-2, -1, 1, 2), shift2=100)      # what rounded_net varies
+
+
+def _stage(net, rng, c, e, variant, io, *, stride=1, res_from=None, res_up2=0, k_split=0, nz=3, seed_affine=True, data=None):
+    """'src' -> the conv under test with epilogue `e` -> 'out' (-> 'out2'), and a sink conv behind each output.  `data`: entries of
+    STAGE_DATA that differ.  net.want_formats: the storage format every named tensor is MEANT to have (assert_formats)."""
+    d = dict(STAGE_DATA, **(data or {}))
+    src_wmax, mags, sink_taps = d['src_wmax'], d['mags'], d['sink_taps']
     from terran_amd import lib
     C, cout, k, groups = c['C'], c['cout'], c['k'], c.get('groups', 1)
     pin = io == 'f32'
-    in_off = 32 if e.get('in_slice') else 0
-    selector(net, rng, 'src', C + in_off, halo=k // 2, wmax=1, f32=variant == 'generic')
+    mode = net.like                                  # whose widths, weights and frames the program has (mode_net)
+    # 'f16': a TA_FMT_F16 tensor has whole 64-channel blocks, so every width and slice offset of 32 above becomes 64 (cout + 64 wide,
+    # read or written at 64), and it takes no in_ch_off: the input slice is dropped.  wide = 8: selector magnitude 1 (MODE_PIXEL_SHIFT)
+    blk = 64 if mode == 'f16' else 32
+    wide = 8 if mode == 'f16' else 16
+    off = lambda v: v // 32 * blk
+    # the tolerance modes: every width a whole block (40 + 64 -> 128), so that the direct drain too meets the mode's format thrice
+    wid = (lambda w: -(-w // blk) * blk) if mode in TOLERANCE_MODES else (lambda w: w)
+    in_off = 32 if e.get('in_slice') and mode != 'f16' else 0
+    selector(net, rng, 'src', C + in_off, halo=k // 2, wmax=src_wmax, f32=src_is_f32(variant, mode))
     kw = dict(stride=stride, groups=groups, variant=lib.CONV_VARIANTS[variant], in_ch_off=in_off, k_split=k_split, relu=bool(e.get('relu')))
     if e.get('res') is not None:
-        selector(net, rng, 'shortcut', cout + 32, k=3, halo=2, wmax=16, f32=pin, stride=2 if res_up2 else stride)
-        kw.update(res='shortcut', res_ch_off=e['res'], res_up2=res_up2)
-    out_total, out_off = c.get('out_total', cout + 64 if e.get('out_slice') else cout), c.get('out_off', 32 if e.get('out_slice') else 0)
+        selector(net, rng, 'shortcut', wid(cout + blk), k=3, halo=2, wmax=wide, f32=pin, stride=2 if res_up2 else stride)
+        kw.update(res='shortcut', res_ch_off=off(e['res']), res_up2=res_up2)
+    out_total, out_off = c.get('out_total', cout + 2 * blk if e.get('out_slice') else cout), c.get('out_off', blk if e.get('out_slice') else 0)
     if out_total != cout:
-        selector(net, rng, 'out', out_total, k=3, halo=1, wmax=16, f32=pin, stride=stride)      # every channel written before
+        selector(net, rng, 'out', out_total, k=3, halo=1, wmax=wide, f32=pin, stride=stride)      # every channel written before
     else:
         net.tensor('out', cout, 1, f32=pin)
     if e.get('out2') is not None:
         if e['out2']:
-            selector(net, rng, 'out2', cout + 32, k=3, halo=1, wmax=16, f32=pin, stride=stride)
+            selector(net, rng, 'out2', wid(cout + blk), k=3, halo=1, wmax=wide, f32=pin, stride=stride)
         else:
             net.tensor('out2', cout, 1, f32=pin)
-        kw.update(out2='out2', out2_ch_off=e['out2'], scale2=rng.choice([-2, -1, 1, 2], cout).astype(np.float64),
-                  shift2=rng.integers(-100, 101, cout).astype(np.float64))
+        kw.update(out2='out2', out2_ch_off=off(e['out2']), scale2=rng.choice(list(d['scale2']), cout).astype(np.float64),
+                  shift2=rng.integers(-d['shift2'], d['shift2'] + 1, cout).astype(np.float64))
     if e.get('prelu'):
         kw['prelu'] = rng.choice([-2, -1, 0, 2, 3], cout).astype(np.float64)
     if e.get('affine'):
         kw['in_affine'] = (rng.choice([-1, 1, 2], C).astype(np.float64), rng.integers(-8, 9, C).astype(np.float64))
-    W, b = stage_weights(rng, cout, C // groups, k, nz=nz, ranges=max(k_split, 1))
+    W, b = stage_weights(rng, cout, C // groups, k, nz=nz, mags=mags, ranges=max(k_split, 1))
+    if mode == 'f16x2':                              # every output channel: one weight with a non-zero lo half
+        for o in range(cout):
+            ci, ky, kx = np.argwhere(W[o])[0]
+            if src_wmax > 1 and ci % 4 < 2:              # 'rounded': the lo-bearing weight sits on a weak channel of 'src' (selector_weights)
+                W[o, ci - ci % 4 + 2, ky, kx], W[o, ci, ky, kx] = W[o, ci, ky, kx], 0.0
+                ci += 2 - ci % 4
+            W[o, ci, ky, kx] *= LO_FACTOR
     net.conv('src', 'out', W, b, out_ch_off=out_off, **kw)
     # the sinks are pinned as well, to another kernel than the one under test: the launch counts then say which conv ran where
     # (40 or 72 channels are no whole K slabs: those sinks are the generic kernel's, as the conv under test is)
     net.sink_variant = sv = 'pipe64' if variant != 'pipe64' and cout % 32 == 0 else ('generic' if pin else 'split_1x4')
-    sink(net, rng, 'out', 'after', out_total, variant=lib.CONV_VARIANTS[sv])
+    if mode == 'f16' and not pin:                    # a TA_FMT_F16 tensor is read by the split-role kernels alone
+        sv = net.sink_variant = 'split_1x4_w2' if variant == 'split_1x4' else 'split_1x4'
+    sink_taps = sink_taps or (X2_SINK_TAPS if mode == 'f16x2' else range(9))
+    sink_mode = SISTER_MODE.get(net.precision)                # (module text: the sinks of 'f16x2' / 'bf16' read both words)
+    # (a width that is no whole block of the mode's format stays float32 though nothing pins it: that sink is the generic kernel's)
+    w2 = wid(cout + off(e['out2'])) if e.get('out2') else cout       # the second sink reads the whole of 'out2'
+    svs = [sv if pin or w % blk == 0 else 'generic' for w in [out_total] + ([w2] if e.get('out2') is not None else [])]
+    sink(net, rng, 'out', 'after', out_total, variant=lib.CONV_VARIANTS[svs[0]], precision=sink_mode, taps=sink_taps)
     if e.get('out2') is not None:
-        sink(net, rng, 'out2', 'after2', cout + e['out2'], variant=lib.CONV_VARIANTS[sv])
+        sink(net, rng, 'out2', 'after2', w2, variant=lib.CONV_VARIANTS[svs[1]], precision=sink_mode, taps=sink_taps)
     n_sel = sum(1 for s in net.steps if s[1] == 'input')
     net.counts = {variant: 1}                                       # what Context.conv_counts() must show after one forward
-    for v, n in (('generic', n_sel), (sv, 2 if e.get('out2') is not None else 1)):
+    for v, n in [('generic', n_sel)] + [(v, 1) for v in svs]:
         net.counts[v] = net.counts.get(v, 0) + n
     if lean_expected(variant, net.precision, e, io, k_split):
         net.counts['lean_epilogue'] = 1
     net.names = [n for n in ('src', 'shortcut', 'out', 'out2', 'after', 'after2') if n in net.tid]
+    # the formats meant: 'src' float32 for the kernels that read nothing else and off the 8-channel grid, the mode's own format
+    # otherwise; shortcut and outputs float32 when pinned or no whole blocks wide; the sinks' outputs float32
+    own = pack.SPLIT_FMT[pack.PRECISIONS[net.precision]]
+    staged = (out_off | kw.get('res_ch_off', 0) | kw.get('out2_ch_off', 0)) % 8 == 0
+    chans = {n: net.P.tensors[net.tid[n]][0] for n in net.names}
+    net.want_formats = {n: pack.FMT_F32 if n.startswith('after') or pin or chans[n] % blk else own for n in net.names}
+    net.want_formats['src'] = pack.FMT_F32 if src_is_f32(variant, mode) or not staged or (mode == 'f16' and groups > 1) else own
     return net
+
+
+def assert_formats(net):
+    """The packer gives every named tensor the format the program was built for (tensor_formats(), not an assumption): a program
+    listed for a drain's TA_FMT_F16 / pre-split store does meet that store."""
+    f = net.P.tensor_formats()
+    got = {n: f[net.tid[n]] for n in net.names}
+    assert got == net.want_formats, (net.precision, got, net.want_formats)
+    return got
+
+
+def mode_net(precision, like=None, family='exact'):
+    """A Net whose frames are shifted as the mode's exactness rule needs (MODE_PIXEL_SHIFT; 0 outside the tolerance modes, and in
+    the 'rounded' family).  like: the program of that mode -- widths, weights, frames, sink taps -- with every op in `precision`."""
+    net = Net(precision, pixel_shift=MODE_PIXEL_SHIFT.get(like or precision, 0) if family == 'exact' else 0, family=family)
+    net.like = like or precision
+    return net
+
+
+X2_SINK_TAPS = (0, 8)
 
 
 def _seed(*key):
@@ -639,13 +855,50 @@ def _seed(*key):
     return zlib.crc32(repr(key).encode())
 
 
-def epilogue_net(precision, case, variant, epi, io='f32'):
+def epilogue_net(precision, case, variant, epi, io='f32', like=None):
     """selector (3 -> C) -> 'src'; a 3x3 selector -> 'shortcut' (32 channels wider than cout, halo 2); the conv of CONV_CASES[case]
     with EPILOGUES[epi], pinned to `variant` -> 'out' (halo 1; a slice of a tensor a 3x3 selector has written where the epilogue or
     the case says so) and 'out2'; sink convs 'after' / 'after2' read both with their halos.  The weights depend on (case, epi) alone:
-    every variant, io and precision of a case computes the same numbers."""
-    c = CONV_CASES[case]
-    return _stage(Net(precision), np.random.default_rng(_seed('epilogue', case, epi)), c, EPILOGUES[epi], variant, io, stride=c.get('stride', 1))
+    every variant, io and precision of a case computes the same numbers.  like='f16x2' with precision 'f16x3': the two-product mode's
+    program (lo-bearing weights, 11-bit activations) in the three-product mode, whose 'out' it then shares bit for bit."""
+    c = all_cases(like or precision)[case]
+    return _stage(mode_net(precision, like), np.random.default_rng(_seed('epilogue', case, epi)), c, EPILOGUES[epi], variant, io, stride=c.get('stride', 1))
+
+
+# ---- the 'rounded' family: the same stage on operands or results that exceed the mode's bit counts (module text) --------------------
+# Frames of the whole 0 .. 255.  'f16': the sums reach several thousand, so the TA_FMT_F16 stores of 'out' / 'out2' round to 11 bits (a
+# float32-pinned 'out' is then rounded when the sink forms its operand); 'bf16': |src| reaches 773, 10 bits, so the conv under test
+# reads bf16_rne(src); 'f16x2': 'src' comes from a selector of magnitude 8 on every fourth channel (|src| <= 6184: 13 bits; <= 773 on
+# channels 2 and 3 of four) and is read as x_hi = f16_rne(src 2^a) 2^-a, a from the packed program's exponents; each output channel has
+# two weights of magnitude 1, the lo-bearing one on a weak channel, and no PReLU slope multiplies the sums: 6184 + 773 + 50 < 2^13 at
+# the quantum 2^-11, exact in float32; what the half-float pair of 'out' / 'out2' cannot hold (22 bits) is rounded by the reference
+# as the store rounds it; each sink has ONE tap, the corner that reads the halo; the second output has scales of +-1 and shifts within
+# 40 (7007 + 40 < 2^13).  The 40-channel case is the generic kernel's direct drain; K in 2 and 4 ranges ends in splitk_reduce_kernel:
+# with the staged and the lean drain of the other programs, every one of the four stores rounds something.
+ROUNDED_CASES = ('c64_3x3', 'c128_3x3', 'c64to64_1x1', 'c128to40in192_1x1')
+ROUNDED_EPILOGUES = {'f16': ('plain', 'prelu_res32_out2', 'res0_out2_slice'), 'bf16': ('plain', 'prelu_res32_out2', 'res0_out2_slice'),
+                     'f16x2': ('plain', 'relu_out2')}
+ROUNDED_KSPLIT = (('c128_3x3', 'res0_out2_slice', 2), ('c128_3x3', 'prelu', 4))      # (case, epilogue, K ranges) on KSPLIT_VARIANTS
+ROUNDED_SIZES = ((3, 5, 3), (3, 9, 10))
+
+
+def rounded_net(precision, case, variant, epi, io='split', k_split=0):
+    c = all_cases(precision)[case]
+    x2 = precision == 'f16x2'
+    data = dict(src_wmax=8, mags=(1, 1, 1, 1), sink_taps=(0,), scale2=(-1, 1), shift2=40) if x2 else None
+    return _stage(mode_net(precision, family='rounded'), np.random.default_rng(_seed('rounded', case, epi, k_split)), c, EPILOGUES[epi], variant, io,
+                  nz=(2 if x2 else 3) + (2 if k_split else 0), k_split=k_split, data=data)
+
+
+def rounded_programs(case, variant, precision):
+    """[(epilogue, io, K ranges)] of ROUNDED_CASES[case] that `variant` can run: pre-split io wherever the kernel has it."""
+    c = all_cases(precision)[case]
+    if not variant_eligible(variant, precision, cout=c['cout'], k=c['k'], cin=c['C'], size=ROUNDED_SIZES[-1], staged=c.get('out_off', 0) % 8 == 0):
+        return []
+    out = [(epi, 'split', 0) for epi in ROUNDED_EPILOGUES[precision]]
+    if variant in KSPLIT_VARIANTS and precision != 'f16x2':       # ('f16x2': four weights of up to 6184 would pass 2^13 at its quantum)
+        out += [(epi, 'split', ks) for cs, epi, ks in ROUNDED_KSPLIT if cs == case]
+    return out
 
 
 UP2_CASES = ('c64_3x3', 'c128_3x3')
@@ -655,15 +908,15 @@ UP2_EPILOGUES = {'relu_res0': dict(relu=True, res=0), 'res32': dict(res=32), 're
 def up2_net(precision, case, variant, epi, io='f32'):
     """As epilogue_net, but 'shortcut' comes from a STRIDE-2 3x3 selector on the same frames -- ceil(h / 2) x ceil(w / 2) -- and the
     conv under test reads it at (y >> 1, x >> 1) (RetinaFace's FPN merge, pack/retinaface.py)."""
-    return _stage(Net(precision), np.random.default_rng(_seed('up2', case, epi)), CONV_CASES[case], UP2_EPILOGUES[epi], variant, io, res_up2=1)
+    return _stage(mode_net(precision), np.random.default_rng(_seed('up2', case, epi)), CONV_CASES[case], UP2_EPILOGUES[epi], variant, io, res_up2=1)
 
 
 def up2_programs(case, variant, precision):
     c = CONV_CASES[case]
     out = []
     for epi in UP2_EPILOGUES:
-        sizes = tuple(s for s in case_sizes(case) if variant_eligible(variant, precision, cout=c['cout'], k=c['k'], size=s, cin=c['C']))
-        out += [(epi, io, sizes) for io in ('f32', 'split') if sizes and not (io == 'split' and (precision == 'f32' or variant == 'generic'))]
+        sizes = tuple(s for s in case_sizes(case, False, precision) if variant_eligible(variant, precision, cout=c['cout'], k=c['k'], size=s, cin=c['C']))
+        out += [(epi, io, sizes) for io in ('f32', 'split') if sizes and not (io == 'split' and (precision == 'f32' or (variant == 'generic' and precision not in TOLERANCE_MODES)))]
     return out
 
 
@@ -677,7 +930,7 @@ KSPLITS = (2, 4)
 def ksplit_net(precision, case, variant, epi, k_split, io='f32'):
     """As epilogue_net with K cut in `k_split` ranges: the kernels write raw partial sums, splitk_reduce_kernel runs the whole epilogue.
     Every output channel has a weight in every range."""
-    return _stage(Net(precision), np.random.default_rng(_seed('ksplit', case, epi, k_split)), KSPLIT_CASES[case], KSPLIT_EPILOGUES[epi],
+    return _stage(mode_net(precision), np.random.default_rng(_seed('ksplit', case, epi, k_split)), KSPLIT_CASES[case], KSPLIT_EPILOGUES[epi],
                   variant, io, k_split=k_split, nz=4)
 
 

@@ -11,7 +11,10 @@
 - the loader's program check accepts every program;
 - the conv output-stage programs of tests/test_gpu_conv_exact.py (epilogue_net, up2_net, ksplit_net): reference == torch, the
   exactness rule through the whole chain, data on which one wrong offset / slope / class / K range / shift changes the answer,
-  the formats each listing assumes, and a per-channel un-scale that is not one value throughout.
+  the formats each listing assumes, and a per-channel un-scale that is not one value throughout;
+- the programs of the tolerance modes (tests/test_gpu_conv_exact_modes.py): the 'exact' family equals plain torch float64 and obeys the
+  per-mode rule, the 'rounded' family equals a second statement of the roundings made of torch.half / torch.bfloat16 casts and does
+  round something; formats, 64-channel slab counts, lo halves in the packed rows, and the deliberate mistakes of ep.MODE_MISTAKES.
 """
 import numpy as np
 import pytest
@@ -24,8 +27,28 @@ from tests import exact_programs as ep
 FMT_OF = {'f32': pack.FMT_F32, 'bf16x3': pack.FMT_SPLIT, 'f16x3': pack.FMT_SPLIT16}
 
 
-def torch_replay(net, fr):
-    """The same recipe on torch-CPU float64 ops."""
+def _cast(v, dt):
+    return v.to(torch.float32).to(dt).to(torch.float64)
+
+
+def _cast_pair(v, dt):
+    hi = _cast(v, dt)
+    return hi + _cast(v - hi, dt)
+
+
+def _stored(net, name, y, ch_off, fmts):
+    """What tensor `name` gives back after y was stored into it: casts at the packer's per-channel exponents."""
+    e = torch.from_numpy(np.ldexp(1.0, net.P.scales[net.tid[name]][ch_off:ch_off + y.shape[1]].astype(np.int32)))[None, :, None, None]
+    f = fmts[net.tid[name]]
+    s = y * e
+    s = _cast(s, torch.half) if f == pack.FMT_F16 else (_cast_pair(s, torch.half) if f == pack.FMT_SPLIT16 else
+                                                       (_cast_pair(s, torch.bfloat16) if f == pack.FMT_SPLIT else _cast(s, torch.float32)))
+    return s / e
+
+
+def torch_replay(net, fr, rounded=False):
+    """The same recipe on torch-CPU float64 ops.  rounded: a program of a tolerance mode, with the mode's roundings as torch casts --
+    the activation operand (half / bfloat16 of the stored value), the weight operand (hi word, or the pair) and every store."""
     x0 = torch.zeros((fr.shape[0], 4) + fr.shape[1:3], dtype=torch.float64)
     x0[:, :3] = torch.from_numpy(fr.astype(np.float64)).permute(0, 3, 1, 2).flip(1)
     t = {'input': x0}
@@ -34,10 +57,20 @@ def torch_replay(net, fr):
         x = t[src]
         if op == 'conv':
             cout, cin = a['W'].shape[:2]
+            Wt = T(a['W'])
+            if rounded:
+                assert a['in_affine'] is None and a['groups'] == 1 and not a['in_ch_off']
+                mode, fmts = a['precision'], net.P.tensor_formats()
+                dt = torch.bfloat16 if mode.startswith('bf16') else torch.half
+                e_in = torch.from_numpy(np.ldexp(1.0, net.P.scales[net.tid[src]].astype(np.int32)))
+                if mode in ('f16', 'f16x2', 'bf16'):
+                    x = _cast(x * e_in[None, :, None, None], dt) / e_in[None, :, None, None]
+                e_w = torch.from_numpy(np.ldexp(1.0, net.P._fold[a['op']]['wexp'][:cout].astype(np.int32)))[:, None, None, None] / e_in[None, :cin, None, None]
+                Wt = (_cast(Wt * e_w, dt) if mode in ('f16', 'bf16') else _cast_pair(Wt * e_w, dt)) / e_w
             xin = x[:, a['in_ch_off']:a['in_ch_off'] + cin * a['groups']]
             if a['in_affine'] is not None:                             # the affine first, the zero padding after it
                 xin = xin * T(a['in_affine'][0])[None, :, None, None] + T(a['in_affine'][1])[None, :, None, None]
-            y = F.conv2d(xin, T(a['W']), T(a['b']), stride=a['stride'], padding=a['pad'], groups=a['groups'])
+            y = F.conv2d(xin, Wt, T(a['b']), stride=a['stride'], padding=a['pad'], groups=a['groups'])
             y = F.prelu(y, T(a['prelu'])) if a['prelu'] is not None else (F.relu(y) if a['relu'] else y)
             y = F.max_pool2d(y, 2, 2) if a['pool'] else y
             if a['res'] is not None:
@@ -47,9 +80,13 @@ def torch_replay(net, fr):
                 y = y + r
             if a['out2'] is not None:
                 z = y * T(a['scale2'])[None, :, None, None] + T(a['shift2'])[None, :, None, None]
+                if rounded:
+                    z = _stored(net, a['out2'], z, a['out2_ch_off'], fmts)
                 full = t[a['out2']].clone() if a['out2'] in t else torch.zeros((y.shape[0], net.P.tensors[net.tid[a['out2']]][0]) + y.shape[2:], dtype=torch.float64)
                 full[:, a['out2_ch_off']:a['out2_ch_off'] + cout] = z
                 t[a['out2']] = full
+            if rounded:
+                y = _stored(net, dst, y, a['out_ch_off'], fmts)
             if dst in t or cout != net.P.tensors[net.tid[dst]][0]:
                 full = t[dst].clone() if dst in t else torch.zeros((y.shape[0], net.P.tensors[net.tid[dst]][0]) + y.shape[2:], dtype=torch.float64)
                 full[:, a['out_ch_off']:a['out_ch_off'] + cout] = y
@@ -381,3 +418,127 @@ def test_conv_stage_programs_load_as_listed(i, precision):
         assert len(np.unique(us)) >= 2, (name, v, io)
         if io == 'split':
             assert len(np.unique(a_out)) >= 2, (name, v, io, a_out)
+
+
+# ---- the tolerance modes: the programs of tests/test_gpu_conv_exact_modes.py -------------------------------------------------------
+FMT_OF_MODE = {'f16': pack.FMT_F16, 'f16x2': pack.FMT_SPLIT16, 'bf16': pack.FMT_SPLIT}
+
+
+def mode_programs(mode):
+    """(id, net of the last listed (variant, io), sizes, stride) of every 'exact' program of `mode`."""
+    out = []
+    for case, c in ep.all_cases(mode).items():
+        for epi in c['epi']:
+            listed = [(v, io, sizes) for v in ep.VARIANTS for e_, io, sizes in ep.conv_programs(case, v, mode) if e_ == epi]
+            if not listed:                                          # ('f16' has no grouped conv, so that case has no listing at all)
+                assert mode == 'f16' and c.get('groups', 1) > 1
+                break
+            v, io, _ = listed[-1]
+            out.append(('epilogue-%s-%s' % (case, epi), ep.epilogue_net(mode, case, v, epi, io), ep.case_sizes(case, ep.EPILOGUES[epi].get('affine'), mode), c.get('stride', 1)))
+    for case in ep.UP2_CASES:
+        for epi in ep.UP2_EPILOGUES:
+            v, io = [(v, io) for v in ep.VARIANTS for e_, io, _ in ep.up2_programs(case, v, mode) if e_ == epi][-1]
+            out.append(('up2-%s-%s' % (case, epi), ep.up2_net(mode, case, v, epi, io), ep.case_sizes(case, False, mode), 1))
+    for case in ep.KSPLIT_CASES:
+        for epi, ks, io in ep.ksplit_programs(case, mode):
+            if io == 'split':
+                out.append(('ksplit%d-%s-%s' % (ks, case, epi), ep.ksplit_net(mode, case, 'split_2x2', epi, ks, io), ep.KSPLIT_SIZES, 1))
+    return out
+
+
+def conv_under_test(net):
+    return net.P.ops[net.conv_ops['out']], [s for s in net.steps if s[1] == 'src' and s[2] == 'out'][0][3]
+
+
+@pytest.mark.parametrize('mode', ep.TOLERANCE_MODES)
+def test_mode_exact_family(mode):
+    """reference == plain torch float64 (so no rounding of the mode changed a value; `reference` asserts the per-mode rule per tensor
+    on the way); the tensors have the mode's own formats; 'f16': n_slabs == taps * cin / 64 and a rows64 image; 'f16x2': every packed
+    weight row of the conv under test has a non-zero lo half; the mistakes of the mode change the answer."""
+    flipped, f16_named = set(), set()
+    for name, net, sizes, stride in mode_programs(mode):
+        lib.check_program(net.P)
+        op, a = conv_under_test(net)
+        f = formats(net)
+        for size in sizes:
+            fr = ep.mode_frames(net, size, stride)
+            ref, want = ep.reference(net, fr), torch_replay(net, fr)
+            for k in ref:
+                assert np.array_equal(ref[k], want[k]), (mode, name, k, size)
+            assert not net.rounding.changed
+            for mistake in ep.MODE_MISTAKES:
+                wrong = ep.reference(net, fr, mistake=mistake)
+                if any(not np.array_equal(wrong[k], ref[k]) for k in ('out', 'out2') if k in ref):
+                    flipped.add(mistake)
+        assert f['src'] in (FMT_OF_MODE[mode], pack.FMT_F32), (name, f)
+        for k in ('src', 'shortcut', 'out', 'out2'):
+            if f.get(k) == FMT_OF_MODE[mode]:
+                f16_named.add(k)
+        taps, cin = op['kh'] * op['kw'], op['cin']
+        if mode == 'f16' and f['src'] == pack.FMT_F16:
+            assert op['n_slabs'] == taps * cin // 64 and net.P._fold[net.conv_ops['out']]['rows64'].shape[0] == op['n_slabs'], name
+        if mode == 'f16x2':
+            k, size = net.P.w._at[op['w_off']]                         # the packed image itself: [slab][coutp][hi x32 | lo x32] half words
+            rows = np.frombuffer(net.P.w.chunks[k], np.uint16).reshape(op['n_slabs'], op['coutp'], 64)
+            assert size == rows.nbytes and np.all(((rows[:, :op['cout'], 32:] & 0x7FFF) != 0).any(axis=(0, 2))), name
+    assert f16_named == {'src', 'shortcut', 'out', 'out2'}, (mode, f16_named)
+    # every listing of every program, not only the one walked above: the formats are the ones meant (tensor_formats() against
+    # net.want_formats), and each drain of DESIGN.md's table meets the mode's own format in 'out', 'out2' and 'shortcut'
+    own, met = FMT_OF_MODE[mode], {}
+    nets = [(('lean' if net.counts.get('lean_epilogue') else 'staged') if io == 'split' and staged else ('direct' if io == 'split' else None), v, net)
+            for case, c in ep.all_cases(mode).items() for v in ep.VARIANTS for staged in [c.get('out_off', 0) % 8 == 0]
+            for epi, io, _ in ep.conv_programs(case, v, mode) for net in [ep.epilogue_net(mode, case, v, epi, io)]]
+    nets += [('lean' if net.counts.get('lean_epilogue') else 'staged' if io == 'split' else None, v, net) for case in ep.UP2_CASES for v in ep.VARIANTS
+             for epi, io, _ in ep.up2_programs(case, v, mode) for net in [ep.up2_net(mode, case, v, epi, io)]]
+    nets += [('reduce%d' % ks if io == 'split' else None, v, net) for case in ep.KSPLIT_CASES for v in ep.KSPLIT_VARIANTS
+             for epi, ks, io in ep.ksplit_programs(case, mode) for net in [ep.ksplit_net(mode, case, v, epi, ks, io)]]
+    for drain, v, net in nets:
+        got = ep.assert_formats(net)
+        if drain:                                                     # the mode's own io: what the drain stores and adds is in the format
+            blk = 64 if mode == 'f16' else 32                         # (the 40-channel case: its own 40-wide 'out2' cannot be of whole blocks)
+            whole = [k for k in ('shortcut', 'out', 'out2') if k in got and net.P.tensors[net.tid[k]][0] % blk == 0]
+            assert all(got[k] == own for k in whole), (mode, drain, v, got)
+            for k in whole:
+                if True:
+                    met.setdefault((drain, 'sym' if v in ('generic', 'pipe64') else 'split'), set()).add(k)
+    every = {'shortcut', 'out', 'out2'}
+    assert met[('direct', 'sym')] == every and met[('staged', 'sym')] == every and met[('staged', 'split')] == every, met
+    assert met[('lean', 'split')] == every and met[('reduce2', 'split')] == every and met[('reduce4', 'split')] == every, met
+    want = {'f16': {'slab64_second_half_swapped'}, 'f16x2': {'x_lo_kept', 'w_lo_dropped'}, 'bf16': set()}[mode]
+    assert flipped >= want - {'x_lo_kept'}, (mode, flipped)       # (x_lo_kept needs an x_lo: the rounded family below)
+
+
+@pytest.mark.parametrize('mode', ep.TOLERANCE_MODES)
+def test_mode_rounded_family(mode):
+    """reference == the torch-cast statement of the mode's roundings, something IS rounded in every program (the stored value in 'f16',
+    an operand in 'f16x2' / 'bf16'), and the mode's mistakes change the answer."""
+    flipped = set()
+    for case in ep.ROUNDED_CASES:
+        for v in ep.VARIANTS:
+            for epi, io, ks in ep.rounded_programs(case, v, mode):
+                net = ep.rounded_net(mode, case, v, epi, io, ks)
+                lib.check_program(net.P)
+                ep.assert_formats(net)
+                changed = set()
+                for size in ep.ROUNDED_SIZES:
+                    fr = ep.mode_frames(net, size)
+                    ref, want = ep.reference(net, fr), torch_replay(net, fr, rounded=True)
+                    for k in ref:
+                        assert np.array_equal(ref[k], want[k]), (mode, case, v, epi, ks, k, size)
+                    changed |= net.rounding.changed
+                    for mistake in ep.MODE_MISTAKES:
+                        wrong = ep.reference(net, fr, mistake=mistake)
+                        if any(not np.array_equal(wrong[k], ref[k]) for k in net.names):
+                            flipped.add(mistake)
+                what = {'f16': ('out', 'store'), 'f16x2': ('src', 'read by f16x2'), 'bf16': ('src', 'read by bf16')}[mode]
+                assert what in changed, (mode, case, v, epi, ks, changed)
+    want = {'f16': {'store_truncated'}, 'f16x2': {'x_lo_kept', 'w_lo_dropped'}, 'bf16': set()}[mode]
+    assert flipped >= want, (mode, flipped)
+
+
+def test_the_mode_rule_refuses_what_the_mode_rounds():
+    """An 'exact' program on frames of the whole 0 .. 255 breaks the bit counts: `reference` says so."""
+    net = ep.epilogue_net('bf16', 'c64_3x3', 'split_1x4', 'plain', 'split')
+    net.pixel_shift = 0
+    with pytest.raises(AssertionError, match='exactness rule'):
+        ep.reference(net, ep.frames(5, 3, 9, 10))
