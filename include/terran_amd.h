@@ -90,8 +90,12 @@ void ta_frames_free(ta_frames* f);
 /* cv2.resize(..., INTER_LINEAR) semantics on the device
  * (face/detection/__init__.py:33-38, pose/openpose/wrapper.py:106-111). */
 int ta_frames_resize(ta_ctx* ctx, const ta_frames* src, int dst_h, int dst_w, ta_frames** out);
-/* Pillow Image.resize(size, resample=BICUBIC) semantics (antialiased separable convolution with
- * 22-bit fixed-point coefficients; arcface/wrapper.py:83-85, the no-landmark crop path). */
+/* Pillow Image.resize(size, resample=BICUBIC) of every image of the batch (arcface/wrapper.py:83-85, the no-landmark
+ * crop path): the pixels are ta_frames_resample's for one whole-frame region per image and TA_RESAMPLE_BICUBIC, without
+ * its 16384 cap on a side.  An empty batch gives an empty (0, dst_h, dst_w) batch.  TA_E_INVALID, before anything is
+ * allocated: a null argument, dst_h or dst_w <= 0, a batch of another device, or a size the launches do not cover --
+ * more than 65535 workgroups along y (dst_h above 4 x 65535, or a resized width with more than 16 x 65535 source rows),
+ * 2^32 threads or more along x (n * ceil(dst_w / 64) * 256), axis tables of 2^32 entries or more. */
 int ta_frames_resize_bicubic(ta_ctx* ctx, const ta_frames* src, int dst_h, int dst_w, ta_frames** out);
 /* Zero-pad `src` image `src_index` into image `dst_index` of `dst` at (top, left)
  * (merge_in, face/detection/__init__.py:96-139 / pose/__init__.py:48-88). */

@@ -340,9 +340,12 @@ int stage(ta_ctx* ctx, const std::vector<rs_rec>& recs, const std::vector<int32_
   return TA_OK;
 }
 
-// Both passes over recs[first .. first + count - 1]; `mid` and `out` are what the records' offsets count from.
-void launch_passes(ta_ctx* ctx, const ta_frames* src, const staged& s, const std::vector<rs_rec>& recs, size_t first, size_t count,
-                   uint8_t* mid, uint8_t* out) {
+// The workgroups both passes take over recs[first .. first + count - 1]: x for both, y of each (0: the pass is not launched).
+struct pass_grid {
+  int tiles_x;
+  size_t x, rows_y, cols_y;
+};
+pass_grid grid_of(const std::vector<rs_rec>& recs, size_t first, size_t count) {
   int max_ow = 0, max_rows = 0, max_oh = 0;
   for (size_t j = first; j < first + count; ++j) {
     const rs_rec& r = recs[j];
@@ -351,12 +354,55 @@ void launch_passes(ta_ctx* ctx, const ta_frames* src, const staged& s, const std
     max_ow = std::max(max_ow, r.ow);
   }
   const int tiles_x = (max_ow + TX - 1) / TX;
-  if (max_rows > 0)
-    hipLaunchKernelGGL(resample_rows, dim3((unsigned)(count * tiles_x), (max_rows + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP), dim3(THREADS),
-                       0, ctx->stream, (const uint8_t*)src->dev, src->h, src->w, s.recs + first, s.tab, mid, out, tiles_x);
-  if (max_oh > 0)
-    hipLaunchKernelGGL(resample_cols, dim3((unsigned)(count * tiles_x), (max_oh + TY - 1) / TY), dim3(THREADS), 0, ctx->stream,
-                       (const uint8_t*)src->dev, src->h, src->w, s.recs + first, s.tab, (const uint8_t*)mid, out, tiles_x);
+  return {tiles_x, count * tiles_x, ((size_t)max_rows + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP, ((size_t)max_oh + TY - 1) / TY};
+}
+
+// Both passes over recs[first .. first + count - 1]; `mid` and `out` are what the records' offsets count from.
+void launch_passes(ta_ctx* ctx, const ta_frames* src, const staged& s, const std::vector<rs_rec>& recs, size_t first, size_t count,
+                   uint8_t* mid, uint8_t* out) {
+  const pass_grid g = grid_of(recs, first, count);
+  if (g.rows_y > 0)
+    hipLaunchKernelGGL(resample_rows, dim3((unsigned)g.x, (unsigned)g.rows_y), dim3(THREADS), 0, ctx->stream, (const uint8_t*)src->dev,
+                       src->h, src->w, s.recs + first, s.tab, mid, out, g.tiles_x);
+  if (g.cols_y > 0)
+    hipLaunchKernelGGL(resample_cols, dim3((unsigned)g.x, (unsigned)g.cols_y), dim3(THREADS), 0, ctx->stream, (const uint8_t*)src->dev,
+                       src->h, src->w, s.recs + first, s.tab, (const uint8_t*)mid, out, g.tiles_x);
+}
+
+// `regions` of `src`, checked by the caller and n > 0 of them, resized to out_w x out_h each into a new batch.  An output
+// the launches cannot cover is refused here, before anything is allocated: a launch has at most 65535 workgroups along
+// y and 2^32 - 1 threads along x, and the tables are addressed in 32 bits.
+int resample_regions(ta_ctx* ctx, const char* who, const ta_frames* src, const ta_resample_region* regions, int n, int out_h, int out_w,
+                     int filter, ta_frames** out) {
+  table_set ts;
+  std::vector<rs_rec> recs;
+  size_t mid_bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const ta_resample_region& q = regions[i];
+    rs_rec r = make_rec(ts, q.frame, 0, 0, src->w, src->h, q.x0, q.y0, q.x1, q.y1, out_w, out_h, filter, &mid_bytes);
+    r.out = (size_t)i * out_h * out_w * 3;
+    recs.push_back(r);
+  }
+  const pass_grid g = grid_of(recs, 0, recs.size());
+  if (g.rows_y > 65535 || g.cols_y > 65535 || g.x * THREADS > UINT32_MAX || ts.tab.size() > UINT32_MAX)
+    return ta_fail(ctx, TA_E_INVALID, "%s: %d images of %d x %d from %d x %d are more than one set of launches covers", who, n, out_w, out_h,
+                   src->w, src->h);
+  ta_frames* dst = nullptr;
+  TA_TRY(ta_frames_alloc_uninit(ctx, n, out_h, out_w, &dst));
+  staged s;
+  int rc = stage(ctx, recs, ts.tab, std::vector<int2>(), mid_bytes, &s);
+  if (rc == TA_OK) {
+    launch_passes(ctx, src, s, recs, 0, recs.size(), s.pixels, dst->dev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);           // pinned / scratch staging is reused by the next call
+    if (e != hipSuccess) rc = ta_fail(ctx, TA_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (rc != TA_OK) {
+    ta_frames_free(dst);
+    return rc;
+  }
+  *out = dst;
+  return TA_OK;
 }
 
 }  // namespace
@@ -397,32 +443,19 @@ extern "C" int ta_frames_resample(ta_ctx* ctx, const ta_frames* src, const ta_re
                      q.x0, q.y0, q.x1, q.y1, W, H);
   }
   if (n == 0) return TA_OK;
+  return resample_regions(ctx, "frames_resample", src, regions, n, out_h, out_w, filter, out);
+}
 
-  table_set ts;
-  std::vector<rs_rec> recs;
-  size_t mid_bytes = 0;
-  for (int i = 0; i < n; ++i) {
-    const ta_resample_region& q = regions[i];
-    rs_rec r = make_rec(ts, q.frame, 0, 0, W, H, q.x0, q.y0, q.x1, q.y1, out_w, out_h, filter, &mid_bytes);
-    r.out = (size_t)i * out_h * out_w * 3;
-    recs.push_back(r);
-  }
-  ta_frames* dst = nullptr;
-  TA_TRY(ta_frames_alloc_uninit(ctx, n, out_h, out_w, &dst));
-  staged s;
-  int rc = stage(ctx, recs, ts.tab, std::vector<int2>(), mid_bytes, &s);
-  if (rc == TA_OK) {
-    launch_passes(ctx, src, s, recs, 0, recs.size(), s.pixels, dst->dev);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);           // pinned / scratch staging is reused by the next call
-    if (e != hipSuccess) rc = ta_fail(ctx, TA_E_DEVICE, "frames_resample: %s", hipGetErrorString(e));
-  }
-  if (rc != TA_OK) {
-    ta_frames_free(dst);
-    return rc;
-  }
-  *out = dst;
-  return TA_OK;
+// The whole of every image of the batch with the BICUBIC filter: one region per image, one axis table for all of them.
+// No 16384 cap on a side, and an empty batch gives an empty batch.
+extern "C" int ta_frames_resize_bicubic(ta_ctx* ctx, const ta_frames* src, int dst_h, int dst_w, ta_frames** out) {
+  ta_enter(ctx);
+  if (!ctx || !src || !out || dst_h <= 0 || dst_w <= 0) return ta_fail(ctx, TA_E_INVALID, "frames_resize_bicubic: bad args");
+  std::vector<ta_resample_region> whole(src->n);
+  for (int i = 0; i < src->n; ++i) whole[i] = {i, 0.f, 0.f, (float)src->w, (float)src->h};
+  TA_TRY(ta_check_batch(ctx, "frames_resize_bicubic", src, whole.data(), src->n));
+  if (src->n == 0) return ta_frames_alloc_uninit(ctx, 0, dst_h, dst_w, out);
+  return resample_regions(ctx, "frames_resize_bicubic", src, whole.data(), src->n, dst_h, dst_w, TA_RESAMPLE_BICUBIC, out);
 }
 
 extern "C" int ta_frames_pixelate(ta_ctx* ctx, ta_frames* frames, const ta_pixelate_region* regions, int n) {

@@ -22,6 +22,16 @@ def bicubic_cases():
     return [(g['bicubic_src_%d' % k], tuple(int(v) for v in size), g['bicubic_out_%d' % k]) for k, size in enumerate(g['bicubic_size'])]
 
 
+# Frames.resize_bicubic on the shared resample kernels (csrc/resample.hip: workgroups of TX = 64 pixels x TY = 4 rows, the
+# horizontal pass walks ROWS_PER_GROUP = 16 rows), as batches of 2: [((n, height, width), (out_h, out_w))]
+BICUBIC_TILE_EDGES = [((2, 17, 130), (5, 65)), ((2, 16, 128), (4, 64)), ((2, 15, 126), (3, 63))]     # one past, on, one short of a tile
+BICUBIC_SKIPS = [((2, 9, 40), (9, 13)), ((2, 9, 40), (4, 40)), ((2, 9, 40), (9, 40))]                # no vertical pass, no horizontal pass, the copy
+# ksize = ceil(2 in / out) * 2 + 1 coefficients per output sample: a horizontal workgroup stages 64 rows of them in 8192
+# LDS words (ksize <= 128), a vertical one 4 rows (ksize <= 2048); beyond that they are read from global memory
+BICUBIC_LDS_SWITCH = [((2, 3, 63), (3, 2)), ((2, 3, 64), (3, 2)), ((2, 1022, 3), (2, 3)), ((2, 1024, 3), (2, 3))]
+BICUBIC_EDGE_CASES = BICUBIC_TILE_EDGES + BICUBIC_SKIPS + BICUBIC_LDS_SWITCH
+
+
 def random_similarity(rng, h, w):
     """6 float64 (crop pixel -> source point of an h x w image): any rotation, scale e^-2 .. e^1.5 source pixels per crop
     pixel, the crop's corner anywhere from 60 pixels before the image to 10 pixels past it."""

@@ -1,5 +1,6 @@
 """Generate tests/golden/align.npz with Pillow alone: what the aligned-crop kernel (csrc/arcface_post.hip warp_kernel) and
-the Pillow-bicubic resize of resident frames (csrc/runtime.hip pil_resample_kernel) have to reproduce at their edges.
+the Pillow-bicubic resize of resident frames (ta_frames_resize_bicubic on csrc/resample.hip's kernels) have to reproduce at
+their edges.
 
     warp cases     Image.fromarray(src).transform((112, 112), Image.AFFINE, matrix, resample=Image.BILINEAR, fillcolor=0),
                    the call of the reference's aligned crop; `warp_names` lists them in order

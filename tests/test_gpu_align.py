@@ -1,6 +1,6 @@
 """-m gpu: the oldest device code of the recognition path at its edges -- the aligned crop (csrc/arcface_post.hip
-warp_kernel), the row normalisation and the cosine matrix of the same file, and the resize / Pillow-bicubic / paste kernels
-of resident frames (csrc/runtime.hip).
+warp_kernel), the row normalisation and the cosine matrix of the same file, the resize and paste kernels of resident frames
+(csrc/frames.hip) and their Pillow-bicubic resize (ta_frames_resize_bicubic on the kernels of csrc/resample.hip).
 
 References: real Pillow through tests/golden/align.npz (tests/golden/make_golden_align.py) for the warp and the bicubic
 resize; beyond the fixture their numpy restatements, which tests/test_align_cpu.py holds bit for bit to the fixture and to
@@ -199,8 +199,9 @@ def test_frames_resize_bicubic_equals_pillow_on_the_fixture(ctx):
 
 
 def test_frames_resize_bicubic_batch_and_grid_stride(ctx):
-    """A batch of 3 (the image stride in both passes), and one 600 x 450 image to 900 x 600: 540 000 pixels, more than the
-    launch's 2048 x 256 threads, so the vertical pass runs its grid-stride loop."""
+    """A batch of 3 (the per-image offsets of the horizontal result and of the output), and one 600 x 450 image to
+    900 x 600: 15 tiles of 64 pixels across, 29 groups of 16 rows in the horizontal pass and 150 groups of 4 rows in the
+    vertical one, the last tile of each partly empty."""
     imgs = align_cases.noise(800, 3, 80, 96, 3)
     got = _bicubic(ctx, imgs, 12, 10)
     for k in range(3):
@@ -208,6 +209,73 @@ def test_frames_resize_bicubic_batch_and_grid_stride(ctx):
     big = align_cases.noise(801, 450, 600, 3)
     assert 900 * 600 > 2048 * 256
     assert np.array_equal(_bicubic(ctx, big[None], 900, 600)[0], arcface_pre.pil_resize_bicubic(big, (900, 600)))
+
+
+def _whole_frames(ctx, imgs, w, h):
+    """Frames.resample of one whole-frame region per image, BICUBIC."""
+    from terran_amd import lib
+    regions = np.zeros(len(imgs), lib.RESAMPLE_DT)
+    regions['frame'], regions['x1'], regions['y1'] = np.arange(len(imgs)), imgs.shape[2], imgs.shape[1]
+    fr = ctx.upload(imgs)
+    try:
+        out = fr.resample(regions, h, w, lib.BICUBIC)
+        try:
+            return out.download()
+        finally:
+            out.free()
+    finally:
+        fr.free()
+
+
+def test_frames_resize_bicubic_equals_resample_of_whole_frames(ctx):
+    """The two entries of the shared resampler agree: every case of the fixture, and a batch of 3."""
+    cases = [(src[None], size) for src, size, _ in align_cases.bicubic_cases()] + [(align_cases.noise(810, 3, 21, 34, 3), (9, 40))]
+    for imgs, (w, h) in cases:
+        got = _bicubic(ctx, imgs, w, h)
+        assert got.shape == (len(imgs), h, w, 3) and np.array_equal(got, _whole_frames(ctx, imgs, w, h)), (imgs.shape, w, h)
+
+
+@pytest.mark.parametrize('shape,size', align_cases.BICUBIC_EDGE_CASES, ids=lambda v: 'x'.join(map(str, v)))
+def test_frames_resize_bicubic_tile_edges_skipped_passes_and_the_lds_switch(ctx, shape, size):
+    """Batches of 2 against the restatement of Pillow.  align_cases.BICUBIC_TILE_EDGES: one pixel and row past, exactly on and
+    one short of the 64-pixel tile, the 16 source rows of a horizontal group and the 4 output rows of a vertical one.
+    BICUBIC_SKIPS: the vertical pass skipped, the horizontal one skipped, both (the result is the input).  BICUBIC_LDS_SWITCH:
+    127 and 129 coefficients per output column, 2045 and 2049 per output row -- the last counts staged in LDS and the first
+    read from global memory (tests/test_resample_cpu.py holds the planned tables to these counts)."""
+    (n, h, w), (oh, ow) = shape, size
+    imgs = align_cases.noise(820 + h + w, n, h, w, 3)
+    got = _bicubic(ctx, imgs, ow, oh)
+    assert got.shape == (n, oh, ow, 3)
+    for k in range(n):
+        assert np.array_equal(got[k], arcface_pre.pil_resize_bicubic(imgs[k], (ow, oh))), k
+    if (oh, ow) == (h, w):
+        assert np.array_equal(got, imgs)
+
+
+def test_frames_resize_bicubic_of_an_empty_batch(ctx):
+    fr = ctx.upload(np.zeros((0, 5, 7, 3), np.uint8))
+    try:
+        out = fr.resize_bicubic(3, 4)
+        try:
+            assert out.shape == (0, 3, 4, 3)
+        finally:
+            out.free()
+    finally:
+        fr.free()
+
+
+def test_frames_resize_bicubic_refusals(ctx):
+    from terran_amd import lib
+    imgs = align_cases.noise(830, 2, 5, 7, 3)
+    fr = ctx.upload(imgs)
+    try:
+        for h, w in [(0, 4), (3, -1)]:
+            with pytest.raises(lib.TerranAmdError) as e:
+                fr.resize_bicubic(h, w)
+            assert e.value.code == lib.E_INVALID and 'frames_resize_bicubic:' in str(e.value), (h, w)
+            assert np.array_equal(fr.download(), imgs)
+    finally:
+        fr.free()
 
 
 # ---- Frames.paste -----------------------------------------------------------------------------------------------------------

@@ -92,6 +92,29 @@ def test_plan_equals_the_oracle_for_whole_axis_bicubic():
         assert np.array_equal(coefs.reshape(-1), oc.reshape(-1).astype(np.int32)), (in_size, out_size)
 
 
+def test_plan_equals_the_oracle_on_the_axes_of_the_resize_bicubic_tests():
+    """ta_frames_resize_bicubic runs on ta_frames_resample's tables: for every (in, out) axis that the GPU tests of
+    Frames.resize_bicubic resize (tests/test_gpu_align.py, tests/test_gpu_pipeline.py) and the embedder's own
+    1920 x 1080 -> 112 x 63, bounds and zero-padded coefficients equal oracle.arcface_pre._resample_coeffs, which
+    tests/test_align_cpu.py holds to Pillow's recorded output."""
+    from oracle import arcface_pre
+    from tests import align_cases
+    from tests.util import golden
+    pins = golden('pil_pins.npz')['resize_in'].shape
+    frames = [(src.shape[:2], (h, w)) for src, (w, h), _ in align_cases.bicubic_cases()]
+    frames += [(shape[1:], size) for shape, size in align_cases.BICUBIC_EDGE_CASES]
+    frames += [((80, 96), (10, 12)), ((450, 600), (600, 900)), ((21, 34), (40, 9)), (pins[:2], (112, 70)), (pins[:2], (40, 61))]
+    axes = {(i, o) for ins, outs in frames for i, o in zip(ins, outs)} | {(1080, 63), (1920, 112), (112, 112)}
+    ksizes = set()
+    for in_size, out_size in sorted(axes):
+        bounds, coefs = lib.resample_plan(in_size, 0, in_size, out_size, lib.BICUBIC)
+        ob, oc = arcface_pre._resample_coeffs(in_size, out_size)
+        assert np.array_equal(bounds, np.asarray(ob, np.int32).reshape(out_size, 2)), (in_size, out_size)
+        assert np.array_equal(coefs, np.asarray(oc, np.int32).reshape(out_size, -1)), (in_size, out_size)
+        ksizes.add(coefs.shape[1])
+    assert {127, 129, 2045, 2049} <= ksizes              # both sides of the kernels' LDS / global coefficient switch
+
+
 def test_pixelate_model_equals_the_pillow_idiom():
     Image = pytest.importorskip('PIL.Image')
     from PIL import ImageDraw
