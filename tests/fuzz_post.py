@@ -15,7 +15,8 @@ from oracle import openpose_post, retinaface_post           # noqa: E402
 from terran_amd import lib, openpose, retinaface, synth     # noqa: E402
 
 
-def rf_case(ctx, rng):
+def rf_inputs(rng):
+    """The random part of rf_case (no GPU): -> (nine heads, H, W, thr, nms, info)."""
     H, W, N = int(rng.integers(8, 200)), int(rng.integers(8, 260)), int(rng.integers(1, 5))
     dens = float(rng.choice([0.0, 0.02, 0.2, 0.6, 1.0]))
     heads = []
@@ -29,6 +30,11 @@ def rf_case(ctx, rng):
         lmk = rng.normal(0, 0.3, (N, 20, fh, fw)).astype(np.float32)
         heads += [prob, bbox, lmk]
     thr, nms = float(rng.choice([0.5, 0.3, 0.75])), float(rng.choice([0.4, 0.2, 0.6]))
+    return heads, H, W, thr, nms, dict(H=H, W=W, N=N, dens=dens, thr=thr, nms=nms)
+
+
+def rf_case(ctx, rng):
+    heads, H, W, thr, nms, info = rf_inputs(rng)
     ref = retinaface_post.postprocess(heads, H, W, thr, nms)
     got = retinaface.postprocess(ctx, heads, H, W, thr, nms)
     ok = [len(g) for g in got] == [len(r) for r in ref]
@@ -37,10 +43,11 @@ def rf_case(ctx, rng):
             for a, b in zip(g, r):
                 ok &= bool(np.array_equal(a['bbox'], b['bbox']) and a['score'] == b['score'] and
                            np.array_equal(a['landmarks'], b['landmarks']))
-    return ok, dict(H=H, W=W, N=N, dens=dens, thr=thr, nms=nms, kept=sum(len(r) for r in ref))
+    return ok, dict(info, kept=sum(len(r) for r in ref))
 
 
-def op_case(ctx, rng):
+def op_inputs(rng):
+    """The random part of op_case (no GPU): -> (heat maps, PAFs, scale, info)."""
     seed = int(rng.integers(0, 1 << 30))
     P, n = int(rng.integers(0, 13)), int(rng.integers(1, 4))
     h, w = int(rng.integers(6, 40)), int(rng.integers(6, 56))
@@ -52,19 +59,24 @@ def op_case(ctx, rng):
         y0, x0 = int(rng.integers(1, h - 8)), int(rng.integers(1, w - 10))
         hm[i, part, y0:y0 + 7, x0:x0 + 9] = float(rng.choice([0.3, 0.5, 0.9]))
         kw = dict(kw, plateau=(i, part))
+    return hm, paf, scale, dict(seed=seed, P=P, n=n, h=h, w=w, scale=scale, **kw)
+
+
+def op_case(ctx, rng):
+    hm, paf, scale, info = op_inputs(rng)
     ref = openpose_post.postprocess(paf, hm, scale)
     try:
         got = openpose.group(ctx, paf, hm, scale)
     except openpose.PoseOverflow as e:              # an image over a device cap: the others must still match
         ok = all(g is None or [(a['keypoints'].tolist(), a['score']) for a in g] == [(b['keypoints'].tolist(), b['score']) for b in r]
                  for g, r in zip(e.results, ref))
-        return ok, dict(seed=seed, P=P, n=n, h=h, w=w, scale=scale, overflow=e.images, **kw)
+        return ok, dict(info, overflow=e.images)
     ok = [len(p) for p in got] == [len(p) for p in ref]
     if ok:
         for gp, rp in zip(got, ref):
             for a, b in zip(gp, rp):
                 ok &= bool(np.array_equal(a['keypoints'], b['keypoints']) and a['score'] == b['score'])
-    return ok, dict(seed=seed, P=P, n=n, h=h, w=w, scale=scale, humans=sum(len(p) for p in ref), **kw)
+    return ok, dict(info, humans=sum(len(p) for p in ref))
 
 
 def main():

@@ -264,3 +264,20 @@ def run_exact(ctx, net, fr, names, what='', ref=None):
         same(m.read(name), ref[name], '%s %s %s' % (what, fr.shape, name))
     frames.free()
     return ref
+
+
+# ---- the detector's production entry, as RetinaFace._detect_arrays calls it -------------------------------------------------------
+def retinaface_run(ctx, model, frames, threshold, nms_threshold, capacity, outputs=True):
+    """One ta_retinaface_run on resident frames with room for `capacity` detections (outputs=False: null output pointers).
+    -> (rc, counts (N,), boxes (capacity, 4), landmarks (capacity, 5, 2), scores (capacity,), required)."""
+    import ctypes as C
+    from terran_amd import lib
+    counts = np.full(len(frames), -1, np.int32)
+    boxes = np.full((max(capacity, 0), 4), np.nan, np.float32)
+    lmks = np.full((max(capacity, 0), 5, 2), np.nan, np.float32)
+    scores = np.full(max(capacity, 0), np.nan, np.float32)
+    req = C.c_int32(-1)
+    out = [lib.ptr(a) if outputs else None for a in (boxes, lmks, scores)]
+    rc = ctx.lib.ta_retinaface_run(model.h, frames.h, float(threshold), float(nms_threshold), int(capacity), lib.ptr(counts),
+                                   out[0], out[1], out[2], C.byref(req))
+    return rc, counts, boxes, lmks, scores, int(req.value)
