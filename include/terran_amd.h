@@ -309,6 +309,66 @@ typedef struct ta_saturate_region {
 } ta_saturate_region;
 int ta_frames_saturate(ta_ctx* ctx, ta_frames* frames, const ta_saturate_region* regions, int n);
 
+/* ---- colour: matrices, YCbCr and HSV conversions, 3-D look-up tables ------------------------- */
+/* Converts the colours of regions of `frames` in place, Pillow's
+ *     im.paste(X(im.crop(box)), box)                      under the ellipse shape only the ellipse's pixels change
+ * bit for bit, where X is the region's op, ops[regions[i].op]:
+ *     TA_COLOR_MATRIX     convert('RGB', m): the 12 floats at tables[table ..], row by row.  Per band, in float32 with
+ *                         every multiply and add rounded on its own: v = m0 r + m1 g + m2 b + m3 (left to right), v + 0.5;
+ *                         0 if v <= 0, 255 if v >= 255, else truncated
+ *     TA_COLOR_RGB2YCBCR  convert('YCbCr'): libImaging's int16 tables at 6 fractional bits, entry (int)(c 64 i + 0.5),
+ *                         (T_R[r] + T_G[g] + T_B[b]) >> 6, + 128 for Cb and Cr
+ *     TA_COLOR_YCBCR2RGB  convert('RGB') of a 'YCbCr' image: the inverse tables over i - 128, clipped to 0 .. 255
+ *     TA_COLOR_RGB2HSV    convert('HSV'): V = max, S = (max - min) / max and H from float32 quotients, each times 255
+ *                         and truncated
+ *     TA_COLOR_HSV2RGB    convert('RGB') of an 'HSV' image
+ *     TA_COLOR_LUT3D      filter(ImageFilter.Color3DLUT(size, table)), 3 channels in and out: size = (s0, s1, s2), every
+ *                         axis 2 .. 65; the 3 s0 s1 s2 floats at tables[table ..] as Pillow stores them, R fastest:
+ *                         entry 3 (r + s0 (g + s1 b)) + channel.  The table is quantised on the host as libImaging does
+ *                         it (the float32 product t * 16320, rounded half away from zero, saturated at +-32767); a node
+ *                         travels as four int16 (8 bytes).  Trilinear interpolation in integers along R, then G, then B.
+ *                         A table of at most 65536 bytes of nodes (up to 20^3) is held in LDS, a larger one is read
+ *                         through the cache.
+ * A batch carries three bytes per pixel and NO mode: after RGB2YCBCR the three bytes of a pixel are Y, Cb, Cr, after
+ * RGB2HSV they are H, S, V, and every other call goes on treating them as R, G, B.  The caller keeps track of what a
+ * region holds, as a Pillow image's mode does.
+ * Regions are as ta_frames_point takes them (half-open box inside the frame, no side longer than 16384, TA_BLUR_BOX or
+ * TA_BLUR_ELLIPSE); ops of different kinds may be mixed in one call.  Regions of one frame apply in list order where they
+ * overlap (rounds of pairwise disjoint regions, one launch per round); regions of different frames may be interleaved.
+ * `tables`: a HOST array of n_tables floats, read by the MATRIX and LUT3D ops; records and tables travel in one staging
+ * copy.  The call runs on `ctx`'s stream (a batch of another context on the same device may be passed) and returns when it
+ * is done.  n = 0: TA_OK.
+ * TA_E_INVALID, before any launch and any changed pixel, naming the region or the op: what ta_frames_point refuses of a
+ * region; an `op` outside 0 .. n_ops - 1; an unknown kind; a LUT3D axis below 2 or above 65; a table that is missing
+ * (tables = NULL, a negative `table`) or reaches past n_tables; a matrix or table entry that is NaN or infinite.  Every
+ * op is checked, used or not. */
+#define TA_COLOR_MATRIX 0
+#define TA_COLOR_RGB2YCBCR 1
+#define TA_COLOR_YCBCR2RGB 2
+#define TA_COLOR_RGB2HSV 3
+#define TA_COLOR_HSV2RGB 4
+#define TA_COLOR_LUT3D 5
+typedef struct ta_color_region {
+  int32_t frame;
+  int32_t x0, y0, x1, y1;
+  int32_t shape;         /* TA_BLUR_*                                 */
+  int32_t op;            /* index into `ops`                          */
+} ta_color_region;
+typedef struct ta_color_op {
+  int32_t kind;          /* TA_COLOR_*                                */
+  int32_t size[3];       /* LUT3D: s0 (R), s1 (G), s2 (B)             */
+  int32_t table;         /* MATRIX, LUT3D: the first float of the op's table in `tables` */
+} ta_color_op;
+int ta_frames_color(ta_ctx* ctx, ta_frames* frames, const ta_color_region* regions, int n, const ta_color_op* ops, int n_ops,
+                    const float* tables, size_t n_tables);
+/* HOST ONLY, no context: what ta_frames_color derives before it launches anything.  rounds[i]: the round region i runs
+ * in, as ta_blur_plan's.  nodes: the int16 entries the device reads, the LUT3D ops' tables one after the other in op
+ * order, four int16 per node (R, G, B entry and 0), s0 s1 s2 nodes per op; nothing for an op of another kind.  Either
+ * output may be NULL.  Frame indices only group the regions here.  TA_E_INVALID: what ta_frames_color refuses without
+ * looking at a frame. */
+int ta_color_plan(const ta_color_region* regions, int n, const ta_color_op* ops, int n_ops, const float* tables, size_t n_tables,
+                  int32_t* rounds, int16_t* nodes);
+
 /* ---- neighbourhood filters: convolution kernels, rank filters, unsharp mask ----------------- */
 /* Filters regions of `frames` in place, Pillow's
  *     im.paste(im.crop(box).filter(F), box[, ellipse mask])

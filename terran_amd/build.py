@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libterran_amd.so')
 SOURCES = ['runtime.hip', 'frames.hip', 'conv_split.hip', 'conv_split_modes.hip', 'conv_sym.hip', 'conv_dwpw.hip', 'conv_igemm.hip', 'layers.hip', 'model_load.hip', 'model_plan.hip', 'model_run.hip', 'retinaface_post.hip', 'arcface_post.hip',
-           'openpose_post.hip', 'draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip', 'combine.hip', 'jpeg_host.hip', 'jpeg.hip',
+           'openpose_post.hip', 'draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip', 'combine.hip', 'color.hip', 'jpeg_host.hip', 'jpeg.hip',
            'jpeg_encode.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
@@ -66,9 +66,10 @@ def build(force=False, verbose=False):
         objs.append(o)
         # bit-exact float steps (draw: Pillow's polygon scan; blur: Pillow's box radius and weights; resample: its coefficients;
         # transform: Pillow's double coordinates and interpolation; tone: Image.blend's float32 multiply and add; filter:
-        # libImaging's float32 kernel sums, the same blend and blur's set-up; combine: the same blend, ImageChops.add's division)
+        # libImaging's float32 kernel sums, the same blend and blur's set-up; combine: the same blend, ImageChops.add's division;
+        # color: convert()'s float32 matrix sums and the HSV conversions' float32 / double steps)
         exact = src.endswith('_post.hip') or src in ('draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip',
-                                                     'combine.hip')
+                                                     'combine.hip', 'color.hip')
         flags = FLAGS + (['-ffp-contract=off'] if exact else []) + extra_all
         want = _unit_hash(s, headers, flags)
         try:

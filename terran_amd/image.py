@@ -40,6 +40,11 @@ functions (usable without a device), and one in-place call per batch.
 Two batches: `paste_frames`, `composite_frames`, `blend_frames`, `chop_frames` / `difference_frames` and `copy_frames` are
 Pillow's `Image.paste`, `Image.composite`, `Image.blend` and the two-image `ImageChops` functions between resident frames
 (`ta_frames_combine`), in place and bit for bit; `pack_combine` builds their records without a device.
+
+Colour: `convert_frames` ('YCbCr', 'HSV' and back, or 'RGB' with a matrix), `matrix_frames`, `color_lut_frames`
+(`ImageFilter.Color3DLUT`) and `hue_frames` are Pillow's `Image.convert` and 3-D table filter on resident frames
+(`ta_frames_color`), in place and bit for bit; `color_spec` builds their op records without a device.  A batch has no
+mode: after a conversion its three bytes per pixel are Y, Cb, Cr or H, S, V, and the caller keeps track of that.
 """
 import os
 from pathlib import Path
@@ -1009,7 +1014,8 @@ def filter_spec(flt):
     `MedianFilter` / `MaxFilter` up to size 7, `UnsharpMask`, and `GaussianBlur` with a scalar radius (kind
     FILTER_GAUSSIAN, which `filter_frames` routes to `ta_frames_blur`) -- or a built-in's lower-case name, which needs no
     Pillow.  A record passes through.  ValueError, naming the filter, for what is not offered: `ModeFilter`, `BoxBlur`, a
-    radius per axis, `MultibandFilter`s such as `Color3DLUT`, rank sizes above 7."""
+    radius per axis, `MultibandFilter`s such as `Color3DLUT` (that one is `color_lut_frames`' and `color_spec`'s, through
+    `ta_frames_color`), rank sizes above 7."""
     if isinstance(flt, np.ndarray) and flt.dtype == lib.FILTER_SPEC_DT and flt.shape == ():
         return flt
     if isinstance(flt, str):
@@ -1085,6 +1091,119 @@ def median_frames(frames, size=3, ctx=None):
     if isinstance(size, (int, np.integer)) and size > FILTER_RANK_LIMIT:
         raise ValueError('median_frames: MedianFilter of size %r: rank filters are offered up to size %d' % (size, FILTER_RANK_LIMIT))
     return filter_frames(frames, rank_spec(size, size * size // 2 if isinstance(size, (int, np.integer)) else size), ctx=ctx)
+
+
+# ---- colour: matrices, YCbCr / HSV, 3-D look-up tables --------------------------------------------------------------------
+COLOR_CONVERSIONS = {'ycbcr': lib.COLOR_RGB2YCBCR, 'rgb_from_ycbcr': lib.COLOR_YCBCR2RGB, 'hsv': lib.COLOR_RGB2HSV,
+                     'rgb_from_hsv': lib.COLOR_HSV2RGB}
+COLOR_LUT_AXIS = (2, 65)                # Color3DLUT's own limits of an axis
+
+
+def color_spec(op):
+    """What a colour call takes -> (a lib.COLOR_OP_DT record whose `table` is 0, its float32 table) for `Frames.color`:
+
+        a 12-tuple                          `convert('RGB', matrix)`
+        'ycbcr', 'rgb_from_ycbcr'           `convert('YCbCr')`, `convert('RGB')` of a 'YCbCr' image
+        'hsv', 'rgb_from_hsv'               `convert('HSV')`, `convert('RGB')` of an 'HSV' image
+        an `ImageFilter.Color3DLUT`, or (size, table): size an int or (s0, s1, s2), table 3 * s0 * s1 * s2 numbers as
+                                            Pillow stores them (R fastest, the three channels of a node together)
+
+    A (record, table) pair passes through.  ValueError for what is not offered: 4-tuples (an 'L' output), 1- and 4-channel
+    tables, an axis outside 2 .. 65, a table of another length, numbers that are not finite."""
+    who = 'color_spec'
+    rec = np.zeros((), lib.COLOR_OP_DT)
+    if isinstance(op, tuple) and len(op) == 2 and isinstance(op[0], np.ndarray) and op[0].dtype == lib.COLOR_OP_DT:
+        return op[0].reshape(()), np.ascontiguousarray(op[1], np.float32).reshape(-1)
+    if isinstance(op, str):
+        if op not in COLOR_CONVERSIONS:
+            raise ValueError('%s: %r is not one of %s' % (who, op, sorted(COLOR_CONVERSIONS)))
+        rec['kind'] = COLOR_CONVERSIONS[op]
+        return rec, np.zeros(0, np.float32)
+    if hasattr(op, 'table') and hasattr(op, 'channels'):            # ImageFilter.Color3DLUT
+        if op.channels != 3 or getattr(op, 'mode', None) not in (None, 'RGB'):
+            raise ValueError('%s: a Color3DLUT of %r channels and target mode %r: three channels in and out are offered'
+                             % (who, op.channels, getattr(op, 'mode', None)))
+        op = (tuple(op.size), op.table)
+    if isinstance(op, (tuple, list)) and len(op) == 2 and not np.isscalar(op[1]):
+        size, table = op
+        size = (size,) * 3 if isinstance(size, (int, np.integer)) and not isinstance(size, bool) else tuple(size)
+        if len(size) != 3 or not all(isinstance(v, (int, np.integer)) and COLOR_LUT_AXIS[0] <= v <= COLOR_LUT_AXIS[1] for v in size):
+            raise ValueError('%s: a 3-D table size of three integers within %d .. %d, got %r' % ((who,) + COLOR_LUT_AXIS + (size,)))
+        table = _finite32(table, 'the table', who).reshape(-1)
+        nodes = size[0] * size[1] * size[2]
+        if len(table) != 3 * nodes:
+            raise ValueError('%s: a table of 3 x %d x %d x %d = %d entries, got %d (1- and 4-channel tables are not offered)'
+                             % ((who,) + size + (3 * nodes, len(table))))
+        rec['kind'], rec['size'] = lib.COLOR_LUT3D, size
+        return rec, np.ascontiguousarray(table)
+    if isinstance(op, (tuple, list, np.ndarray)) and len(op) == 12:
+        rec['kind'] = lib.COLOR_MATRIX
+        return rec, np.ascontiguousarray(_finite32(op, 'the matrix', who).reshape(-1))
+    if isinstance(op, (tuple, list, np.ndarray)) and len(op) == 4:
+        raise ValueError("%s: a 4-tuple converts to 'L': only 12-tuples ('RGB' output) are offered" % who)
+    raise ValueError('%s: %r is not a 12-tuple, one of %s, a Color3DLUT or (size, table)' % (who, op, sorted(COLOR_CONVERSIONS)))
+
+
+def _color(who, frames, op, boxes=None, shape='box', ctx=None):
+    if shape not in _SHAPES:
+        raise ValueError("%s: shape must be 'box' or 'ellipse', got %r" % (who, shape))
+    rec, table = color_spec(op)
+    batches, _ = _batches(frames, who)
+    for b, q in zip(batches, _frame_boxes(batches, boxes, who)):
+        if len(q):
+            b.color(_regions(lib.COLOR_REGION_DT, q, _SHAPES[shape]), rec, table, ctx=ctx)
+    return frames
+
+
+def convert_frames(frames, mode, matrix=None, source='RGB', boxes=None, shape='box', ctx=None):
+    """Pillow's `Image.convert(mode[, matrix])` of every resident frame, in place (`ta_frames_color`, one call per batch);
+    returns `frames`.  `source` is the mode the frames' bytes are in now: a batch carries three bytes per pixel and no
+    mode, so the caller says it.  Offered: source 'RGB' to 'YCbCr', 'HSV', or 'RGB' with a 12-tuple `matrix`; source
+    'YCbCr' or 'HSV' to 'RGB'.  `boxes`, `shape`: as `filter_frames` takes them."""
+    who = 'convert_frames'
+    if matrix is not None:
+        if (source, mode) != ('RGB', 'RGB'):
+            raise ValueError("%s: a matrix converts 'RGB' to 'RGB' here, got %r to %r" % (who, source, mode))
+        op = matrix
+    else:
+        op = {('RGB', 'YCbCr'): 'ycbcr', ('YCbCr', 'RGB'): 'rgb_from_ycbcr', ('RGB', 'HSV'): 'hsv', ('HSV', 'RGB'): 'rgb_from_hsv'}.get((source, mode))
+        if op is None:
+            raise ValueError("%s: %r to %r is not offered ('RGB' to 'YCbCr' or 'HSV' and back are)" % (who, source, mode))
+    return _color(who, frames, op, boxes, shape, ctx)
+
+
+def matrix_frames(frames, matrix, boxes=None, shape='box', ctx=None):
+    """`im.convert('RGB', matrix)` of every resident frame, in place: a 12-tuple, row by row (white balance, channel
+    mixing, sepia, a camera's colour matrix)."""
+    if not isinstance(matrix, (tuple, list, np.ndarray)) or len(matrix) != 12:
+        raise ValueError("matrix_frames: a 12-tuple ('RGB' output), got %r" % (matrix,))
+    return _color('matrix_frames', frames, matrix, boxes, shape, ctx)
+
+
+def color_lut_frames(frames, lut, boxes=None, shape='box', ctx=None):
+    """`im.filter(ImageFilter.Color3DLUT(size, table))` of every resident frame, in place: `lut` is the Pillow object or
+    (size, table), three channels in and out, every axis 2 .. 65."""
+    rec, table = color_spec(lut)
+    if rec['kind'] != lib.COLOR_LUT3D:
+        raise ValueError('color_lut_frames: a Color3DLUT or (size, table), got %r' % (lut,))
+    return _color('color_lut_frames', frames, (rec, table), boxes, shape, ctx)
+
+
+def hue_lut(shift):
+    """`point()`'s table of `hue_frames`: (h + shift) mod 256 on the first band, the other two as they are."""
+    if not isinstance(shift, (int, np.integer)) or isinstance(shift, bool):
+        raise ValueError('hue_frames: shift must be an integer (256 is a full turn), got %r' % (shift,))
+    i = np.arange(256)
+    return np.concatenate([(i + int(shift)) % 256, i, i]).astype(np.uint8)
+
+
+def hue_frames(frames, shift, ctx=None):
+    """Turn the hue of every resident frame by `shift` / 256 of a full turn, in place: `convert('HSV')`, `point()` with
+    (h + shift) mod 256 on H, `convert('RGB')`, equal to the same three Pillow steps."""
+    table = hue_lut(shift)
+    convert_frames(frames, 'HSV', ctx=ctx)
+    point_frames(frames, table, ctx=ctx)
+    return convert_frames(frames, 'RGB', source='HSV', ctx=ctx)
 
 
 _SUBSAMPLING = {-1: 2, 0: 0, 1: 1, 2: 2, '4:4:4': 0, '4:2:2': 1, '4:2:0': 2}

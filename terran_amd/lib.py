@@ -64,6 +64,8 @@ SIGNATURES = {
     'ta_frames_saturate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_frames_filter': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
     'ta_filter_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    'ta_frames_color': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t]),
+    'ta_color_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     'ta_frames_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
@@ -179,6 +181,41 @@ COMBINE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<
                        ('mask_kind', '<i4'), ('mask_value', '<i4'), ('mask_frame', '<i4'), ('mask_x', '<i4'), ('mask_y', '<i4'),
                        ('mask_band', '<i4')])
 assert COMBINE_DT.itemsize == 72
+
+# ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
+COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
+COLOR_REGION_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('shape', '<i4'),
+                            ('op', '<i4')])
+assert COLOR_REGION_DT.itemsize == 28
+COLOR_OP_DT = np.dtype([('kind', '<i4'), ('size', '<i4', (3,)), ('table', '<i4')])
+assert COLOR_OP_DT.itemsize == 20
+
+
+def _color_args(ops, tables):
+    ops = np.ascontiguousarray(ops, dtype=COLOR_OP_DT).reshape(-1)
+    tables = np.ascontiguousarray(tables if tables is not None else [], dtype=np.float32).reshape(-1)
+    return ops, tables
+
+
+def color_plan(regions, ops, tables=None):
+    """Host only (no context, no device): ta_color_plan -> (round of every region, a list with one entry per op: the int16
+    (s2, s1, s0, 4) nodes the device reads for a COLOR_LUT3D op -- R, G, B entry and 0 --, None for another kind): what
+    ta_frames_color derives from a COLOR_REGION_DT array, a COLOR_OP_DT array and their float32 tables before it launches
+    anything."""
+    lib = load()
+    regions, p, n = _records(regions, COLOR_REGION_DT)
+    ops, tables = _color_args(ops, tables)
+    counts = [int(np.prod(o['size'], dtype=np.int64)) if o['kind'] == COLOR_LUT3D and o['size'].min() >= 2 and o['size'].max() <= 65 else 0 for o in ops]
+    rounds, nodes = np.zeros(n, np.int32), np.zeros(4 * sum(counts) + 4, np.int16)
+    rc = lib.ta_color_plan(p, n, ptr(ops) if len(ops) else None, len(ops), ptr(tables) if len(tables) else None, len(tables),
+                           ptr(rounds), ptr(nodes))
+    if rc != OK:
+        raise TerranAmdError(rc, 'color_plan: a bad box, shape or op index, or an op ta_frames_color refuses')
+    out, at = [], 0
+    for o, c in zip(ops, counts):
+        out.append(nodes[at:at + 4 * c].reshape(int(o['size'][2]), int(o['size'][1]), int(o['size'][0]), 4) if c else None)
+        at += 4 * c
+    return rounds, out
 
 
 def filter_plan(regions, specs):
@@ -696,6 +733,18 @@ class Frames:
         ctx = ctx or self.ctx
         regions, p, n = _records(regions, SATURATE_DT)
         ctx.check(ctx.lib.ta_frames_saturate(ctx.h, self.h, p, n))
+
+    def color(self, regions, ops, tables=None, ctx=None):
+        """Convert the colours of `regions` (a COLOR_REGION_DT array, in order) of this batch in place (ta_frames_color):
+        Pillow's convert('RGB', matrix), convert('YCbCr' / 'HSV') and back, or filter(Color3DLUT) of each half-open box,
+        pasted back under its shape.  `ops`: a COLOR_OP_DT array, a region's `op` names its entry; `tables`: the float32
+        array the matrix and 3-D table ops index with `table` (terran_amd.image.color_spec makes both).  The batch has no
+        mode: after a conversion to YCbCr or HSV its bytes are those bands.  `ctx`: the CALLER's, as in `blur`."""
+        ctx = ctx or self.ctx
+        regions, p, n = _records(regions, COLOR_REGION_DT)
+        ops, tables = _color_args(ops, tables)
+        ctx.check(ctx.lib.ta_frames_color(ctx.h, self.h, p, n, ptr(ops) if len(ops) else None, len(ops),
+                                          ptr(tables) if len(tables) else None, len(tables)))
 
     def filter(self, regions, specs, ctx=None):
         """Filter `regions` (a FILTER_REGION_DT array, in order) of this batch in place (ta_frames_filter): Pillow's

@@ -38,7 +38,7 @@ import random
 
 import numpy as np
 
-from . import lib
+from . import image, lib
 
 # the default 10-colour categorical d3 palette
 PALETTE = [tuple(int(h[i:i + 2], 16) for i in (0, 2, 4)) for h in
@@ -430,7 +430,6 @@ def face_stats(frames, faces_per_frame, margin=0.0, shape='box', mode='RGB', ctx
     draws into the box as Stat's mask -- a dict of arrays (n_faces, 3) or (n_faces, 1), plus 'histogram', the uint32 counts
     they come from; `index` the int32 (n_faces, 2) (frame, face) pairs, as `crop_faces` returns them.  (None, []) when
     there is no face.  Choosing the best-exposed chip of a track is an argmax over these."""
-    from . import image
     _check_batch(frames, faces_per_frame)
     if mode not in lib.HIST_MODES:
         raise ValueError("mode must be 'RGB' or 'L', got %r" % (mode,))
@@ -563,6 +562,29 @@ def blur_faces(frames, faces_per_frame, radius=None, margin=0.0, shape='box', ct
     return frames
 
 
+def pack_color(faces_per_frame, shapes, margin=0.0, shape='box'):
+    """-> lib.COLOR_REGION_DT array with op 0: pack_blur's regions (the same margin, truncation, clipping and order).
+    Host only."""
+    if shape not in BLUR_SHAPES:
+        raise ValueError("shape must be 'box' or 'ellipse', got %r" % (shape,))
+    boxes = _clipped_boxes(faces_per_frame, shapes, margin)
+    q = np.zeros(len(boxes), lib.COLOR_REGION_DT)
+    for r, (f, _, x0, y0, x1, y1) in zip(q, boxes):
+        r['frame'], r['x0'], r['y0'], r['x1'], r['y1'], r['shape'] = f, x0, y0, x1, y1, BLUR_SHAPES[shape]
+    return q
+
+
+def color_faces(frames, faces_per_frame, op, margin=0.0, shape='box', ctx=None):
+    """Convert the colours of the faces of the resident batch `frames` in place (ta_frames_color): `op` is what
+    terran_amd.image.color_spec takes -- a 12-tuple matrix, 'ycbcr' / 'hsv' and back, a Color3DLUT or (size, table) --, so a
+    grade, a tint or a desaturating matrix shows only in the faces.  The boxes, their clipping and their order are
+    blur_faces'."""
+    _check_batch(frames, faces_per_frame)
+    rec, table = image.color_spec(op)
+    frames.color(pack_color(faces_per_frame, frames.shape, margin, shape), rec, table, ctx=ctx)
+    return frames
+
+
 # ---- two batches: a processed copy inside the face boxes, chips back into the frame ------------------------------------
 def pack_composite(faces_per_frame, shapes, other_frames=None, margin=0.0, shape='box', alpha=None):
     """-> lib.COMBINE_DT array: pack_blur's regions (the same margin, truncation, clipping and order) as PASTE records that
@@ -645,7 +667,6 @@ def filter_faces(frames, faces_per_frame, flt, margin=0.0, shape='box', ctx=None
     """Filter the faces of the resident batch `frames` (lib.Frames) in place, Pillow's `crop(box).filter(flt)` pasted back
     under `shape`: sharpen soft faces before they are cropped, denoise them, take their edges.  The boxes, their clipping
     and their order are blur_faces'; `flt`: what `image.filter_spec` takes (a GaussianBlur goes the way of blur_faces)."""
-    from . import image
     _check_batch(frames, faces_per_frame)
     spec = image.filter_spec(flt)
     if spec['kind'] == image.FILTER_GAUSSIAN:
