@@ -247,6 +247,59 @@ typedef struct ta_transform_region {
  * outside 1 .. 16384; a frame index out of range; an unknown method; a coefficient the method reads that is not finite. */
 int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_transform_region* regions, int n, int out_h, int out_w,
                         int filter, const uint8_t* fill_rgb, ta_frames** out);
+/* Pillow's Image.transform(size, MESH, [(box, quad), ...], resample, fillcolor=) -- and with it QUAD, a mesh of the one cell
+ * ((0, 0, out_w, out_h), quad), and ImageOps.deform -- on uint8 RGB, bit for bit.  A cell maps its `box` of the OUTPUT
+ * (half-open, ints) onto the quadrilateral `quad` of the INPUT, corners in Pillow's order nw, sw, se, ne, (x, y) each.
+ * In double, unfused, left to right, with w = x1 - x0, h = y1 - y0, As = 1.0 / w, At = 1.0 / h:
+ *     a0 = nw.x, a1 = (ne.x - nw.x) * As, a2 = (sw.x - nw.x) * At, a3 = (se.x - sw.x - ne.x + nw.x) * As * At
+ *     a4 = nw.y, a5 = (ne.y - nw.y) * As, a6 = (sw.y - nw.y) * At, a7 = (se.y - sw.y - ne.y + nw.y) * As * At
+ * The box is clamped to the output, cx0 = max(x0, 0), cy0 = max(y0, 0), cx1 = min(x1, out_w), cy1 = min(y1, out_h), and
+ * for every pixel (x, y) of the clamped box
+ *     xin = (x - cx0) + 0.5, yin = (y - cy0) + 0.5          (relative to the CLAMPED origin while w, h are the unclamped
+ *     xs = a0 + a1 xin + a2 yin + a3 xin yin                  box's: Pillow's behaviour for a box that starts left of or
+ *     ys = a4 + a5 xin + a6 yin + a7 xin yin                  above the output)
+ * A point with 0 <= xs < W && 0 <= ys < H gives the pixel the filter's sample there, the taps of ta_frames_transform's
+ * PERSPECTIVE route (NEAREST: (int) of the point).  A point outside makes the pixel 0 without a fill colour and leaves it
+ * as it is with one.  The output starts as the fill colour (zeros without one) and the cells apply in list order: they may
+ * overlap, leave gaps and reach outside the output.  Non-finite points count as outside, as in ta_frames_transform. */
+typedef struct ta_mesh_cell {
+  int32_t x0, y0, x1, y1; /* the cell's box of the output, half-open            */
+  double quad[8];         /* nw.x, nw.y, sw.x, sw.y, se.x, se.y, ne.x, ne.y     */
+} ta_mesh_cell;
+typedef struct ta_mesh_image {
+  int32_t frame; /* image index in the batch                           */
+  int32_t mesh;  /* which mesh warps it: cells mesh_first[mesh] .. mesh_first[mesh + 1] - 1 */
+} ta_mesh_image;
+/* The output is cut into tiles of TA_MESH_TILE_W x TA_MESH_TILE_H pixels, one workgroup each; the host bins every mesh's
+ * cells into the tiles their clamped boxes touch. */
+#define TA_MESH_TILE_W 64
+#define TA_MESH_TILE_H 16
+#define TA_MESH_MAX_CELLS (1 << 20)   /* cells of one call                                           */
+#define TA_MESH_MAX_ENTRIES (1 << 24) /* of one call: (cell, tile) pairs, and n_meshes x tiles + 1   */
+/* *out: a NEW batch (n_images, out_h, out_w, 3), owned by `ctx`; image i is
+ *     Image.fromarray(src[images[i].frame]).transform((out_w, out_h), MESH, the cells of mesh images[i].mesh, filter, fillcolor=fill)
+ * mesh_first: n_meshes + 1 ascending offsets into `cells`.  A mesh is built, binned and staged once per call, however many
+ * images share it; ONE launch serves all images, and every pixel is written once: a lane walks its tile's cells from the
+ * last to the first and takes the first whose clamped box holds its pixel (with a fill colour: and whose point lies inside
+ * the source), else the fill.  fill_rgb = NULL is fillcolor=None.  filter: TA_RESAMPLE_NEAREST, _BILINEAR or _BICUBIC.
+ * Images may name frames and meshes in any order and any number of times; a mesh may be empty.  Returns when done.
+ * n_images = 0: TA_OK and *out = NULL.  TA_E_INVALID, before any launch (*out = NULL): a negative count; another filter;
+ * out_h or out_w outside 1 .. 16384; offsets that do not ascend from >= 0 to <= n_cells; a box with x1 <= x0 or y1 <= y0
+ * (Pillow divides by zero or draws nothing there) or a coordinate beyond +-2^24; a corner that is not finite; a frame or
+ * mesh index out of range; more than TA_MESH_MAX_CELLS cells; more than TA_MESH_MAX_ENTRIES tile entries.  A box partly or
+ * wholly outside the output is valid. */
+int ta_frames_transform_mesh(ta_ctx* ctx, const ta_frames* src, const ta_mesh_cell* cells, int n_cells, const int32_t* mesh_first,
+                             int n_meshes, const ta_mesh_image* images, int n_images, int out_h, int out_w, int filter,
+                             const uint8_t* fill_rgb, ta_frames** out);
+/* HOST ONLY, no context: what ta_frames_transform_mesh derives from ONE mesh and an output size before it launches anything.
+ * coefs[8 i .. 8 i + 7]: a0 .. a7 of cell i; boxes[4 i .. 4 i + 3]: its clamped box cx0, cy0, cx1, cy1 (empty when the
+ * cell lies outside the output); tile_first[t], t = 0 .. tiles (tiles = ceil(out_w / TA_MESH_TILE_W) x
+ * ceil(out_h / TA_MESH_TILE_H), row-major): tile t's cells are tile_cells[tile_first[t] .. tile_first[t + 1] - 1], in list
+ * order.  Any output may be NULL.  *n_entries is set whenever the arguments are valid; TA_E_CAPACITY when it exceeds
+ * `capacity` (nothing else written: call with capacity 0 to size tile_cells).  TA_E_INVALID: what ta_frames_transform_mesh
+ * refuses about cells and output size. */
+int ta_mesh_plan(const ta_mesh_cell* cells, int n_cells, int out_h, int out_w, double* coefs, int32_t* boxes, int32_t* tile_first,
+                 int32_t* tile_cells, int capacity, int* n_entries);
 /* Image.transpose(op) of every image of the batch into a NEW batch, owned by `ctx`: (n, h, w, 3) for the flips and
  * ROTATE_180, (n, w, h, 3) for the four ops that swap the axes (ROTATE_90 is counter-clockwise, as in Pillow).  The op
  * codes are Pillow's.  One launch, a tiled copy through LDS.  TA_E_INVALID (*out = NULL): an unknown op. */

@@ -1,5 +1,5 @@
-// ta_frames_transform / ta_frames_transpose: Pillow's `Image.transform(size, AFFINE | PERSPECTIVE, data, resample, fillcolor=)`
-// and `Image.transpose(op)` on uint8 RGB, bit for bit, over a resident frame batch.
+// ta_frames_transform / ta_frames_transform_mesh / ta_frames_transpose: Pillow's `Image.transform(size, AFFINE | PERSPECTIVE |
+// MESH, data, resample, fillcolor=)` and `Image.transpose(op)` on uint8 RGB, bit for bit, over a resident frame batch.
 //
 // Image.transform (libImaging/Geometry.c) maps every OUTPUT pixel centre to a source point in double,
 //   xin = x + 0.5, yin = y + 0.5;  xs = a0 xin + a1 yin + a2, ys = a3 xin + a4 yin + a5;  perspective: both / (a6 xin + a7 yin + 1)
@@ -21,6 +21,12 @@
 // uniform loads); a lane owns 4 consecutive pixels of the region's output image in raster order, 12 bytes, and stores them
 // as three dwords when the image starts on a dword (always when out_h * out_w is a multiple of 4, else for every fourth
 // image), byte by byte otherwise and for the ragged tail at the image's end.  The source is gathered with byte loads.
+// ta_frames_transform_mesh: Image.transform(size, MESH | QUAD, ...) (ImageOps.deform).  An output image is assembled from
+// cells, each a box of the output with a bilinear map of its own (quad_transform: xs = a0 + a1 xin + a2 yin + a3 xin yin
+// with xin, yin relative to the box's CLAMPED origin), applied in list order; they may overlap, leave gaps and reach
+// outside.  No rounds: the host bins a mesh's cells into the 64 x 16 tiles of the output they touch (CSR, list order),
+// once per call however many images share the mesh, and mesh_kernel -- one launch, one workgroup per tile and image, the
+// same 4 pixels and packed store per lane -- lets every pixel pick the LAST cell that Pillow would have let write it.
 // transpose_kernel: a 32 x 32 pixel tile goes through LDS (one dword per pixel, rows padded to 33) so that, for the four
 // ops that swap the axes, consecutive lanes read consecutive source pixels AND write consecutive output pixels.
 #include "frame_regions.h"
@@ -77,24 +83,10 @@ __device__ inline double cubic(double v1, double v2, double v3, double v4, doubl
   return p1 + d * (p2 + d * (p3 + d * p4));
 }
 
-// the pixel (packed R | G << 8 | B << 16) of output position (x, y)
+// the filter's sample (packed R | G << 8 | B << 16) at a source point that passed the inside test
 template <int FILTER>
-__device__ inline uint32_t sample(const tf_rec& q, const int32_t* __restrict__ tab, const source& s, int x, int y, uint32_t fill) {
-  if (FILTER == TA_RESAMPLE_NEAREST) {
-    if (q.route == ROUTE_SCALE) {
-      const int sx = tab[q.xtab + x], sy = tab[q.ytab + y];
-      return sx >= 0 && sy >= 0 ? s.at(sy, sx) : fill;
-    }
-    if (q.route == ROUTE_FIXED) {                       // int32 arithmetic that wraps as Pillow's repeated additions do
-      const int sx = (int32_t)((uint32_t)q.f[2] + (uint32_t)y * (uint32_t)q.f[1] + (uint32_t)x * (uint32_t)q.f[0]) >> 16;
-      const int sy = (int32_t)((uint32_t)q.f[5] + (uint32_t)y * (uint32_t)q.f[4] + (uint32_t)x * (uint32_t)q.f[3]) >> 16;
-      return sx >= 0 && sx < s.W && sy >= 0 && sy < s.H ? s.at(sy, sx) : fill;
-    }
-    double xs, ys;
-    return source_point(q, x, y, s, &xs, &ys) ? s.at((int)ys, (int)xs) : fill;
-  }
-  double xs, ys;
-  if (!source_point(q, x, y, s, &xs, &ys)) return fill;
+__device__ inline uint32_t sample_at(const source& s, double xs, double ys) {
+  if (FILTER == TA_RESAMPLE_NEAREST) return s.at((int)ys, (int)xs);
   xs -= 0.5, ys -= 0.5;
   const double fx = floor(xs), fy = floor(ys);
   const double dx = xs - fx, dy = ys - fy;
@@ -133,6 +125,36 @@ __device__ inline uint32_t sample(const tf_rec& q, const int32_t* __restrict__ t
   return out;
 }
 
+// the pixel (packed R | G << 8 | B << 16) of output position (x, y)
+template <int FILTER>
+__device__ inline uint32_t sample(const tf_rec& q, const int32_t* __restrict__ tab, const source& s, int x, int y, uint32_t fill) {
+  if (FILTER == TA_RESAMPLE_NEAREST) {
+    if (q.route == ROUTE_SCALE) {
+      const int sx = tab[q.xtab + x], sy = tab[q.ytab + y];
+      return sx >= 0 && sy >= 0 ? s.at(sy, sx) : fill;
+    }
+    if (q.route == ROUTE_FIXED) {                       // int32 arithmetic that wraps as Pillow's repeated additions do
+      const int sx = (int32_t)((uint32_t)q.f[2] + (uint32_t)y * (uint32_t)q.f[1] + (uint32_t)x * (uint32_t)q.f[0]) >> 16;
+      const int sy = (int32_t)((uint32_t)q.f[5] + (uint32_t)y * (uint32_t)q.f[4] + (uint32_t)x * (uint32_t)q.f[3]) >> 16;
+      return sx >= 0 && sx < s.W && sy >= 0 && sy < s.H ? s.at(sy, sx) : fill;
+    }
+  }
+  double xs, ys;
+  return source_point(q, x, y, s, &xs, &ys) ? sample_at<FILTER>(s, xs, ys) : fill;
+}
+
+// a lane's `count` <= 4 consecutive pixels to d: three dwords when all four are there and d is on a dword, bytes otherwise
+__device__ inline void store_pixels(uint8_t* d, const uint32_t* px, int count, bool on_dword) {
+  if (count == PIXELS_PER_LANE && on_dword) {
+    uint32_t* d4 = (uint32_t*)d;
+    d4[0] = px[0] | (px[1] << 24);
+    d4[1] = (px[1] >> 8) | (px[2] << 16);
+    d4[2] = (px[2] >> 16) | (px[3] << 8);
+  } else {
+    for (int j = 0; j < count; ++j) d[3 * j] = (uint8_t)px[j], d[3 * j + 1] = (uint8_t)(px[j] >> 8), d[3 * j + 2] = (uint8_t)(px[j] >> 16);
+  }
+}
+
 // grid.x = regions x groups; region r's image is out + r * oh * ow * 3
 template <int FILTER>
 __global__ __launch_bounds__(THREADS) void transform_kernel(const uint8_t* __restrict__ frames, int H, int W, const tf_rec* __restrict__ recs,
@@ -156,15 +178,60 @@ __global__ __launch_bounds__(THREADS) void transform_kernel(const uint8_t* __res
     }
   }
   const size_t image = (size_t)r * npix * 3;
-  uint8_t* d = out + image + (size_t)p0 * 3;            // p0 * 3 is a multiple of 12
-  if (count == PIXELS_PER_LANE && (image & 3) == 0) {
-    uint32_t* d4 = (uint32_t*)d;
-    d4[0] = px[0] | (px[1] << 24);
-    d4[1] = (px[1] >> 8) | (px[2] << 16);
-    d4[2] = (px[2] >> 16) | (px[3] << 8);
-  } else {
-    for (int j = 0; j < count; ++j) d[3 * j] = (uint8_t)px[j], d[3 * j + 1] = (uint8_t)(px[j] >> 8), d[3 * j + 2] = (uint8_t)(px[j] >> 16);
+  store_pixels(out + image + (size_t)p0 * 3, px, count, (image & 3) == 0);      // p0 * 3 is a multiple of 12
+}
+
+// ---- mesh ------------------------------------------------------------------------------------------------------------
+// A cell as the device reads it: the box clamped to the output (empty: the cell is in no tile's list) and a0 .. a7.
+struct mesh_rec {              // 80 bytes
+  int32_t x0, y0, x1, y1;
+  double a[8];
+};
+static_assert(sizeof(mesh_rec) == 80, "mesh_rec");
+constexpr int MESH_TW = TA_MESH_TILE_W, MESH_TH = TA_MESH_TILE_H, MESH_LANES_X = MESH_TW / PIXELS_PER_LANE;
+static_assert(MESH_TW * MESH_TH == THREADS * PIXELS_PER_LANE && MESH_TW % PIXELS_PER_LANE == 0, "one lane per 4 pixels of a tile");
+
+// grid.x = images x tiles.  A workgroup owns one tile of one image; its cell list first[mesh * tiles + tile] .. is the same
+// for all its lanes, so the list and the records come through uniform loads.  A lane owns 4 consecutive pixels of a row and
+// walks the list from the LAST cell to the first: a pixel is settled by the first cell whose clamped box holds it and --
+// under a fill colour (keep), where Pillow leaves a pixel whose point is outside as it is -- whose point is inside the
+// source.  What no cell settles, and what a cell settles with a point outside, is the fill.  Every pixel is written once.
+template <int FILTER>
+__global__ __launch_bounds__(THREADS) void mesh_kernel(const uint8_t* __restrict__ frames, int H, int W, const mesh_rec* __restrict__ recs,
+                                                       const int32_t* __restrict__ first, const int32_t* __restrict__ list,
+                                                       const ta_mesh_image* __restrict__ images, uint8_t* __restrict__ out, int oh, int ow,
+                                                       int tiles_x, int tiles, uint32_t fill, int keep) {
+  const int i = blockIdx.x / tiles, t = blockIdx.x - i * tiles;
+  const ta_mesh_image im = images[i];
+  const int ty = t / tiles_x, tx = t - ty * tiles_x;
+  const int y = ty * MESH_TH + threadIdx.x / MESH_LANES_X, x = tx * MESH_TW + (threadIdx.x % MESH_LANES_X) * PIXELS_PER_LANE;
+  if (y >= oh || x >= ow) return;
+  const int count = min(PIXELS_PER_LANE, ow - x);
+  const size_t at = (size_t)im.mesh * tiles + t;
+  const int begin = first[at], end = first[at + 1];
+  const source s = {frames + (size_t)im.frame * H * W * 3, H, W};
+  double xs[PIXELS_PER_LANE], ys[PIXELS_PER_LANE];
+  unsigned pending = (1u << count) - 1, inside = 0;
+  for (int e = end - 1; e >= begin && pending; --e) {
+    const mesh_rec& c = recs[list[e]];
+    if (y < c.y0 || y >= c.y1) continue;
+    const double yin = (double)(y - c.y0) + 0.5;
+#pragma unroll
+    for (int j = 0; j < PIXELS_PER_LANE; ++j) {
+      if (!((pending >> j) & 1) || x + j < c.x0 || x + j >= c.x1) continue;
+      const double xin = (double)(x + j - c.x0) + 0.5;
+      const double u = c.a[0] + c.a[1] * xin + c.a[2] * yin + c.a[3] * xin * yin;
+      const double v = c.a[4] + c.a[5] * xin + c.a[6] * yin + c.a[7] * xin * yin;
+      const bool in = u >= 0.0 && u < (double)W && v >= 0.0 && v < (double)H;      // false for NaN
+      if (in) xs[j] = u, ys[j] = v, inside |= 1u << j;
+      if (in || !keep) pending &= ~(1u << j);
+    }
   }
+  uint32_t px[PIXELS_PER_LANE];
+#pragma unroll
+  for (int j = 0; j < PIXELS_PER_LANE; ++j) px[j] = (inside >> j) & 1 ? sample_at<FILTER>(s, xs[j], ys[j]) : fill;
+  uint8_t* d = out + ((size_t)i * oh * ow + (size_t)y * ow + x) * 3;
+  store_pixels(d, px, count, ((size_t)d & 3) == 0);
 }
 
 // NEAREST, ROUTE_ACCUM: one thread per output row of such a region
@@ -245,6 +312,92 @@ struct scale_tabs {
     seen.emplace(key, at);
     return at;
   }
+};
+
+// ---- mesh: the host plan -------------------------------------------------------------------------------------------------
+constexpr int MESH_COORD_LIMIT = 1 << 24;
+
+const char* mesh_cell_defect(const ta_mesh_cell& c) {
+  if (c.x1 <= c.x0 || c.y1 <= c.y0) return "empty or inverted box";
+  for (int32_t v : {c.x0, c.y0, c.x1, c.y1})
+    if (v < -MESH_COORD_LIMIT || v > MESH_COORD_LIMIT) return "a box coordinate beyond +-2^24";
+  for (double v : c.quad)
+    if (!isfinite(v)) return "a corner that is not finite";
+  return nullptr;
+}
+
+// What is wrong with a call's cells and output size whatever its frames, or nullptr; *cell: the cell it is about, or -1.
+const char* mesh_defect(const ta_mesh_cell* cells, int n_cells, int out_h, int out_w, int* cell) {
+  *cell = -1;
+  if (n_cells < 0 || (n_cells > 0 && !cells)) return "bad args";
+  if (out_h <= 0 || out_w <= 0 || out_h > MAX_OUT || out_w > MAX_OUT) return "output sides must be 1 .. 16384";
+  if (n_cells > TA_MESH_MAX_CELLS) return "more than TA_MESH_MAX_CELLS cells";
+  for (int i = 0; i < n_cells; ++i)
+    if (const char* why = mesh_cell_defect(cells[i])) {
+      *cell = i;
+      return why;
+    }
+  return nullptr;
+}
+
+// Pillow's QUAD coefficients (Image.__transformer) and the box clamped as ImagingGenericTransform clamps it
+mesh_rec mesh_record(const ta_mesh_cell& c, int out_h, int out_w) {
+  mesh_rec r;
+  const double* q = c.quad;                           // nw 0, 1; sw 2, 3; se 4, 5; ne 6, 7
+  const double As = 1.0 / (c.x1 - c.x0), At = 1.0 / (c.y1 - c.y0);
+  r.a[0] = q[0], r.a[1] = (q[6] - q[0]) * As, r.a[2] = (q[2] - q[0]) * At, r.a[3] = (q[4] - q[2] - q[6] + q[0]) * As * At;
+  r.a[4] = q[1], r.a[5] = (q[7] - q[1]) * As, r.a[6] = (q[3] - q[1]) * At, r.a[7] = (q[5] - q[3] - q[7] + q[1]) * As * At;
+  r.x0 = std::max(c.x0, 0), r.y0 = std::max(c.y0, 0), r.x1 = std::min(c.x1, out_w), r.y1 = std::min(c.y1, out_h);
+  return r;
+}
+
+// The meshes of a call over one output size: a record per cell and, in CSR form, the cells of every (mesh, tile) in list
+// order.  first[m * tiles + t] .. first[m * tiles + t + 1] - 1 index `list`, whose entries index `recs`.
+struct mesh_plan {
+  int tiles_x = 0, tiles = 0;
+  std::vector<mesh_rec> recs;
+  std::vector<int32_t> first, list;
+
+  // false: more than TA_MESH_MAX_ENTRIES (cell, tile) pairs or first indices.  The cells are valid (mesh_defect).
+  bool build(const ta_mesh_cell* cells, const int32_t* mesh_first, int n_meshes, int out_h, int out_w) {
+    tiles_x = (out_w + MESH_TW - 1) / MESH_TW;
+    tiles = tiles_x * ((out_h + MESH_TH - 1) / MESH_TH);
+    const int n_cells = n_meshes ? mesh_first[n_meshes] : 0;
+    if ((int64_t)n_meshes * tiles + 1 > TA_MESH_MAX_ENTRIES) return false;
+    recs.resize(n_cells);
+    int64_t entries = 0;
+    for (int i = 0; i < n_cells; ++i) {
+      const mesh_rec& r = recs[i] = mesh_record(cells[i], out_h, out_w);
+      if (r.x1 > r.x0 && r.y1 > r.y0) entries += (int64_t)span(r.x0, r.x1, MESH_TW) * span(r.y0, r.y1, MESH_TH);
+    }
+    if (entries > TA_MESH_MAX_ENTRIES) return false;
+    first.assign((size_t)n_meshes * tiles + 1, 0);
+    list.resize((size_t)entries);
+    for (int pass = 0; pass < 2; ++pass) {              // count into first[.. + 1], sum, then fill in list order
+      for (int m = 0; m < n_meshes; ++m) {
+        int32_t* f = first.data() + (size_t)m * tiles;
+        for (int i = mesh_first[m]; i < mesh_first[m + 1]; ++i) {
+          const mesh_rec& r = recs[i];
+          if (r.x1 <= r.x0 || r.y1 <= r.y0) continue;
+          for (int ty = r.y0 / MESH_TH; ty <= (r.y1 - 1) / MESH_TH; ++ty)
+            for (int tx = r.x0 / MESH_TW; tx <= (r.x1 - 1) / MESH_TW; ++tx) {
+              if (pass == 0) ++f[ty * tiles_x + tx + 1];
+              else list[(size_t)f[ty * tiles_x + tx]++] = i;
+            }
+        }
+      }
+      if (pass == 0) {
+        for (size_t k = 1; k < first.size(); ++k) first[k] += first[k - 1];
+      } else {                                          // every first[k] now holds its tile's end: shift back
+        for (size_t k = first.size() - 1; k > 0; --k) first[k] = first[k - 1];
+        first[0] = 0;
+      }
+    }
+    return true;
+  }
+
+ private:
+  static int span(int lo, int hi, int tile) { return (hi - 1) / tile - lo / tile + 1; }
 };
 
 }  // namespace
@@ -332,6 +485,93 @@ extern "C" int ta_frames_transform(ta_ctx* ctx, const ta_frames* src, const ta_t
     return rc;
   }
   *out = dst;
+  return TA_OK;
+}
+
+extern "C" int ta_frames_transform_mesh(ta_ctx* ctx, const ta_frames* src, const ta_mesh_cell* cells, int n_cells, const int32_t* mesh_first,
+                                        int n_meshes, const ta_mesh_image* images, int n_images, int out_h, int out_w, int filter,
+                                        const uint8_t* fill_rgb, ta_frames** out) {
+  const char* who = "frames_transform_mesh";
+  ta_enter(ctx);
+  if (!ctx) return TA_E_INVALID;
+  if (out) *out = nullptr;
+  if (!out) return ta_fail(ctx, TA_E_INVALID, "%s: bad args", who);
+  TA_TRY(ta_check_batch(ctx, who, src, images, n_images));
+  if (filter != TA_RESAMPLE_NEAREST && filter != TA_RESAMPLE_BILINEAR && filter != TA_RESAMPLE_BICUBIC)
+    return ta_fail(ctx, TA_E_INVALID, "%s: filter %d, must be NEAREST, BILINEAR or BICUBIC", who, filter);
+  if (n_meshes < 0 || (n_meshes > 0 && !mesh_first)) return ta_fail(ctx, TA_E_INVALID, "%s: bad args", who);
+  int cell;
+  if (const char* why = mesh_defect(cells, n_cells, out_h, out_w, &cell))
+    return cell < 0 ? ta_fail(ctx, TA_E_INVALID, "%s: %s (%d cells, output %d x %d)", who, why, n_cells, out_w, out_h)
+                    : ta_fail(ctx, TA_E_INVALID, "%s: cell %d: %s", who, cell, why);
+  for (int m = 0; m < n_meshes; ++m)
+    if (mesh_first[m] < 0 || mesh_first[m + 1] < mesh_first[m] || mesh_first[m + 1] > n_cells)
+      return ta_fail(ctx, TA_E_INVALID, "%s: mesh %d: cells %d .. %d, the offsets must ascend within 0 .. %d", who, m, mesh_first[m],
+                     mesh_first[m + 1], n_cells);
+  const int N = src->n, H = src->h, W = src->w;
+  for (int i = 0; i < n_images; ++i) {
+    TA_TRY(ta_check_frame(ctx, who, i, images[i].frame, N));
+    if (images[i].mesh < 0 || images[i].mesh >= n_meshes)
+      return ta_fail(ctx, TA_E_INVALID, "%s: image %d: mesh %d out of range [0, %d)", who, i, images[i].mesh, n_meshes);
+  }
+  mesh_plan plan;
+  if (!plan.build(cells, mesh_first, n_meshes, out_h, out_w))
+    return ta_fail(ctx, TA_E_INVALID, "%s: more than %d tile entries", who, TA_MESH_MAX_ENTRIES);
+  if (n_images == 0) return TA_OK;
+  if ((int64_t)n_images * plan.tiles > 0x7fffffffLL)
+    return ta_fail(ctx, TA_E_INVALID, "%s: %d images of %d x %d are more than one launch holds", who, n_images, out_w, out_h);
+  const uint32_t fill = fill_rgb ? (uint32_t)fill_rgb[0] | ((uint32_t)fill_rgb[1] << 8) | ((uint32_t)fill_rgb[2] << 16) : 0u;
+
+  ta_frames* dst = nullptr;
+  TA_TRY(ta_frames_alloc_uninit(ctx, n_images, out_h, out_w, &dst));
+  ta_staging st;                                    // one H2D copy: cell records, the tile lists, the image records
+  const size_t o_rec = st.put(plan.recs), o_first = st.put(plan.first), o_list = st.put(plan.list);
+  const size_t o_img = st.put(images, (size_t)n_images * sizeof(ta_mesh_image));
+  int rc = st.commit(ctx);                          // a code, no return: dst is freed below on every failure
+  if (rc == TA_OK) {
+    const mesh_rec* drec = st.dev<const mesh_rec>(o_rec);
+    const int32_t *dfirst = st.dev<const int32_t>(o_first), *dlist = st.dev<const int32_t>(o_list);
+    const ta_mesh_image* dimg = st.dev<const ta_mesh_image>(o_img);
+    const dim3 grid((unsigned)(n_images * plan.tiles)), block(THREADS);
+    const uint8_t* in = src->dev;
+    const int keep = fill_rgb != nullptr;
+    if (filter == TA_RESAMPLE_NEAREST)
+      hipLaunchKernelGGL(mesh_kernel<TA_RESAMPLE_NEAREST>, grid, block, 0, ctx->stream, in, H, W, drec, dfirst, dlist, dimg, dst->dev, out_h, out_w,
+                         plan.tiles_x, plan.tiles, fill, keep);
+    else if (filter == TA_RESAMPLE_BILINEAR)
+      hipLaunchKernelGGL(mesh_kernel<TA_RESAMPLE_BILINEAR>, grid, block, 0, ctx->stream, in, H, W, drec, dfirst, dlist, dimg, dst->dev, out_h, out_w,
+                         plan.tiles_x, plan.tiles, fill, keep);
+    else
+      hipLaunchKernelGGL(mesh_kernel<TA_RESAMPLE_BICUBIC>, grid, block, 0, ctx->stream, in, H, W, drec, dfirst, dlist, dimg, dst->dev, out_h, out_w,
+                         plan.tiles_x, plan.tiles, fill, keep);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);             // pinned / scratch staging is reused by the next call
+    if (e != hipSuccess) rc = ta_fail(ctx, TA_E_DEVICE, "%s: %s", who, hipGetErrorString(e));
+  }
+  if (rc != TA_OK) {
+    ta_frames_free(dst);
+    return rc;
+  }
+  *out = dst;
+  return TA_OK;
+}
+
+extern "C" int ta_mesh_plan(const ta_mesh_cell* cells, int n_cells, int out_h, int out_w, double* coefs, int32_t* boxes, int32_t* tile_first,
+                            int32_t* tile_cells, int capacity, int* n_entries) {
+  int cell;
+  if (!n_entries || mesh_defect(cells, n_cells, out_h, out_w, &cell)) return TA_E_INVALID;
+  const int32_t mesh_first[2] = {0, n_cells};
+  mesh_plan plan;
+  if (!plan.build(cells, mesh_first, 1, out_h, out_w)) return TA_E_INVALID;
+  *n_entries = (int)plan.list.size();
+  if (*n_entries > capacity) return TA_E_CAPACITY;
+  for (int i = 0; i < n_cells; ++i) {
+    const mesh_rec& r = plan.recs[i];
+    if (coefs) memcpy(coefs + 8 * (size_t)i, r.a, sizeof(r.a));
+    if (boxes) boxes[4 * i] = r.x0, boxes[4 * i + 1] = r.y0, boxes[4 * i + 2] = r.x1, boxes[4 * i + 3] = r.y1;
+  }
+  if (tile_first) memcpy(tile_first, plan.first.data(), plan.first.size() * sizeof(int32_t));
+  if (tile_cells && *n_entries) memcpy(tile_cells, plan.list.data(), plan.list.size() * sizeof(int32_t));
   return TA_OK;
 }
 

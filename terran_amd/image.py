@@ -29,6 +29,10 @@ mixed-size list from `open_images` becomes a batch of a common size (for `encode
 `transform_frames`, `transpose_frames` and `rotate_frames` are Pillow's `Image.transform` (AFFINE, PERSPECTIVE),
 `Image.transpose` and `Image.rotate` on resident batches (`ta_frames_transform`, `ta_frames_transpose`), bit for bit:
 sideways video turned upright, a tilted camera de-rotated, a screen or a sign perspective-corrected, without a download.
+`mesh_frames`, `quad_frames` and `extent_frames` are the other three methods of `Image.transform` -- MESH (which is
+`ImageOps.deform`), QUAD and EXTENT -- the first two on `ta_frames_transform_mesh`, bit for bit; `undistort_cells` /
+`undistort_mesh` build the mesh that removes a lens's Brown-Conrady distortion and `undistort_frames` warps resident frames
+through it.
 
 Pixel values: `histogram_frames` / `frame_stats` are Pillow's `Image.histogram` and `ImageStat.Stat` of resident frames
 (`ta_frames_histogram`; only the counts leave the device), and `point_frames`, `equalize_frames`, `autocontrast_frames`,
@@ -423,6 +427,295 @@ def rotate_frames(frames, angle, resample='nearest', expand=False, center=None, 
         out = b.transform(regions, height, width, lib.NEAREST if kind == 'copy' else code, fill, ctx=on)
         outs.append(out)
     return outs if listed else outs[0]
+
+
+# ---- Image.transform's other methods: MESH (ImageOps.deform), QUAD, EXTENT -------------------------------------------------
+class _MeshTarget:
+    """What a deformer's `getmesh(image)` is called with in place of a Pillow image: `.size`, `.width`, `.height`."""
+
+    def __init__(self, width, height):
+        self.size, self.width, self.height = (width, height), width, height
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+
+def _quad(quad, who):
+    """8 finite numbers nw.x, nw.y, sw.x, sw.y, se.x, se.y, ne.x, ne.y -> a tuple of floats."""
+    try:
+        q = tuple(float(v) for v in quad)
+    except (TypeError, ValueError):
+        q = ()
+    if len(q) != 8 or not np.isfinite(q).all():
+        raise ValueError('%s: a quad must be 8 finite numbers (nw, sw, se, ne; x, y each), got %r' % (who, quad))
+    return q
+
+
+def _looks_like_cell(item):
+    try:
+        return len(item) == 2 and len(item[0]) == 4 and len(item[1]) == 8
+    except TypeError:
+        return False
+
+
+def pack_mesh(mesh, who='pack_mesh'):
+    """Pillow's mesh [(box, quad), ...] -> a lib.MESH_CELL_DT array, cells in order.  `box`: four ints (x0, y0, x1, y1) of the
+    OUTPUT, half-open, x0 < x1 and y0 < y1 (Pillow divides by zero or draws nothing otherwise), within +-2^24, inside the
+    output or not; `quad`: 8 finite numbers, the corners nw, sw, se, ne of the INPUT quadrilateral.  Host only."""
+    if isinstance(mesh, np.ndarray) and mesh.dtype == lib.MESH_CELL_DT:       # packed before: only the values are checked
+        boxes = np.stack([mesh[k].reshape(-1) for k in ('x0', 'y0', 'x1', 'y1')], 1).astype(np.int64)
+        quads = mesh['quad'].reshape(-1, 8)
+    else:
+        try:
+            rows = list(mesh)
+        except TypeError:
+            raise ValueError('%s: a mesh must be a list of (box, quad), got %r' % (who, mesh)) from None
+        for k, item in enumerate(rows):
+            if not _looks_like_cell(item):
+                raise ValueError('%s: cell %d must be ((x0, y0, x1, y1), 8 numbers), got %r' % (who, k, item))
+            if not all(_is_int(v) and abs(int(v)) <= lib.MESH_COORD_LIMIT for v in item[0]):
+                raise ValueError('%s: cell %d: the box must be four ints within +-2^24, got %r' % (who, k, tuple(item[0])))
+        boxes = np.array([tuple(r[0]) for r in rows], np.int64).reshape(-1, 4)
+        try:
+            quads = np.array([tuple(r[1]) for r in rows], np.float64).reshape(-1, 8)
+        except (TypeError, ValueError):
+            quads = np.full((len(rows), 8), np.nan)
+            for k, r in enumerate(rows):
+                quads[k] = _quad(r[1], '%s: cell %d' % (who, k))
+    bad = (np.abs(boxes) > lib.MESH_COORD_LIMIT).any(1)
+    if bad.any():
+        raise ValueError('%s: cell %d: the box must lie within +-2^24, got %r' % (who, bad.argmax(), tuple(boxes[bad.argmax()])))
+    bad = (boxes[:, 2] <= boxes[:, 0]) | (boxes[:, 3] <= boxes[:, 1])
+    if bad.any():
+        raise ValueError('%s: cell %d: the box %r must have x0 < x1 and y0 < y1' % (who, bad.argmax(), tuple(boxes[bad.argmax()])))
+    bad = ~np.isfinite(quads).all(1)
+    if bad.any():
+        _quad(quads[bad.argmax()], '%s: cell %d' % (who, bad.argmax()))
+    cells = np.zeros(len(boxes), lib.MESH_CELL_DT)
+    cells['x0'], cells['y0'], cells['x1'], cells['y1'] = boxes.T
+    cells['quad'] = quads
+    return cells
+
+
+def _run_mesh(who, batches, per_batch, size, code, fill, ctx):
+    """per_batch[i]: (cells, mesh_first, mesh of every frame) of batch i -> the one new batch."""
+    width, height = size
+    if max(len(c) for c, _, _ in per_batch) > lib.MESH_MAX_CELLS:
+        raise ValueError('%s: more than %d cells for one batch' % (who, lib.MESH_MAX_CELLS))
+    ctx = ctx if ctx is not None else batches[0].ctx
+    parts = []
+    try:
+        for b, (cells, first, of_frame) in zip(batches, per_batch):
+            n = b.shape[0]
+            if not n:
+                continue
+            images = np.zeros(n, lib.MESH_IMAGE_DT)
+            images['frame'], images['mesh'] = np.arange(n), of_frame
+            parts.append(b.transform_mesh(cells, first, images, height, width, code, fill, ctx=ctx))
+    except Exception:
+        _free(parts)
+        raise
+    return _one_batch(ctx, parts, height, width)
+
+
+def _mesh_size(batches, size, who):
+    if size is not None:
+        return _size(size, who)
+    sizes = {(b.shape[2], b.shape[1]) for b in batches}
+    if len(sizes) != 1:
+        raise ValueError('%s: size is needed when the frames differ in size' % who)
+    return _size(sizes.pop(), who)
+
+
+def mesh_frames(frames, mesh, size=None, resample='nearest', fillcolor=None, ctx=None):
+    """Resident frames warped through a mesh -> one NEW resident `lib.Frames` (sum(n), height, width, 3), images in input
+    order, each Pillow's `Image.fromarray(frame).transform(size, Image.MESH, mesh, resample=resample, fillcolor=fillcolor)`
+    bit for bit (`ta_frames_transform_mesh`), which is also `ImageOps.deform`.  `frames`: a `lib.Frames` batch or a list of
+    them (as `open_images` returns for mixed sizes); `mesh`: Pillow's list of (box, quad) -- `pack_mesh` has the rules --,
+    one list for all frames (or what `pack_mesh` made of it: a caller that warps batch after batch through one mesh packs
+    it once) or a list of such lists, one per frame, or a deformer: an object whose `getmesh(image)` returns
+    the list, called once per batch with a stand-in that has `.size`, `.width` and `.height` of the batch's frames; `size`:
+    (width, height) of the output, default the frames' own (they must then agree); `resample`: 'nearest', 'bilinear',
+    'bicubic' or Pillow's code; `fillcolor`: None (zeros, and a cell's pixels whose point leaves the source become 0) or
+    (r, g, b) (such pixels keep what lay there).  A shared mesh is built and sent once per batch however many frames it
+    warps.  Every argument is checked before anything is launched."""
+    who = 'mesh_frames'
+    batches, _ = _batches(frames, who)
+    width, height = _mesh_size(batches, size, who)
+    code = _transform_filter(resample, who)
+    fill = _fillcolor(fillcolor, who)
+    total = sum(b.shape[0] for b in batches)
+    if total == 0:
+        raise ValueError('%s: no images' % who)
+    per_batch = []
+    if hasattr(mesh, 'getmesh'):
+        for b in batches:
+            cells = pack_mesh(mesh.getmesh(_MeshTarget(b.shape[2], b.shape[1])), who)
+            per_batch.append((cells, [0, len(cells)], 0))
+    else:
+        packed = isinstance(mesh, np.ndarray) and mesh.dtype == lib.MESH_CELL_DT
+        try:
+            rows = mesh if packed else list(mesh)
+        except TypeError:
+            raise ValueError('%s: mesh must be a list of (box, quad), one such list per frame, or have getmesh()' % who) from None
+        if packed or all(_looks_like_cell(r) for r in rows):    # one mesh (an empty one: all fill)
+            cells = pack_mesh(rows, who)
+            per_batch = [(cells, [0, len(cells)], 0)] * len(batches)
+        elif len(rows) == total:
+            packed = [pack_mesh(r, '%s: frame %d' % (who, k)) for k, r in enumerate(rows)]
+            at = 0
+            for b in batches:
+                mine = packed[at:at + b.shape[0]]
+                at += b.shape[0]
+                first = np.concatenate([[0], np.cumsum([len(c) for c in mine])]).astype(np.int32)
+                cells = np.concatenate(mine) if mine else np.zeros(0, lib.MESH_CELL_DT)
+                per_batch.append((cells, first, np.arange(b.shape[0])))
+        else:
+            raise ValueError('%s: mesh must be a list of (box, quad) or one such list for each of the %d frames' % (who, total))
+    return _run_mesh(who, batches, per_batch, (width, height), code, fill, ctx)
+
+
+def quad_frames(frames, size, quad, resample='nearest', fillcolor=None, ctx=None):
+    """Pillow's `Image.transform(size, Image.QUAD, quad, resample, fillcolor=)` of every resident frame, bit for bit: the
+    quadrilateral `quad` of the frame -- 8 numbers, the corners nw, sw, se, ne as (x, y) -- stretched over a size[0] x
+    size[1] image (a screen, a whiteboard, a plate cut out by its corners).  One quad for all frames or one per frame.
+    It is `mesh_frames` with the one cell ((0, 0) + size, quad); the other arguments and the result are as there."""
+    who = 'quad_frames'
+    batches, _ = _batches(frames, who)
+    width, height = _size(size, who)
+    code = _transform_filter(resample, who)
+    fill = _fillcolor(fillcolor, who)
+    total = sum(b.shape[0] for b in batches)
+    if total == 0:
+        raise ValueError('%s: no images' % who)
+    try:
+        q = np.asarray(quad, np.float64)
+    except (TypeError, ValueError):
+        q = np.zeros(0)
+    shared = q.shape == (8,)
+    if not shared and q.shape != (total, 8):
+        raise ValueError('%s: quad must be 8 numbers, or 8 for each of the %d frames' % (who, total))
+    if not np.isfinite(q).all():
+        raise ValueError('%s: quad must be finite' % who)
+    per_batch, at = [], 0
+    for b in batches:
+        n = 1 if shared else b.shape[0]
+        cells = np.zeros(n, lib.MESH_CELL_DT)
+        cells['x1'], cells['y1'] = width, height
+        cells['quad'] = q if shared else q[at:at + n]
+        per_batch.append((cells, np.arange(n + 1), 0 if shared else np.arange(n)))
+        at += b.shape[0]
+    return _run_mesh(who, batches, per_batch, (width, height), code, fill, ctx)
+
+
+def extent_data(size, extent):
+    """Pillow's AFFINE coefficients for `Image.transform(size, Image.EXTENT, extent)`: the rectangle (x0, y0, x1, y1) of the
+    source stretched over the output, ((x1 - x0) / width, 0, x0, 0, (y1 - y0) / height, y0).  Host only."""
+    width, height = size
+    x0, y0, x1, y1 = extent
+    return ((x1 - x0) / width, 0, x0, 0, (y1 - y0) / height, y0)
+
+
+def extent_frames(frames, size, extent, resample='nearest', fillcolor=None, ctx=None):
+    """Pillow's `Image.transform(size, Image.EXTENT, extent, resample, fillcolor=)` of every resident frame, bit for bit:
+    the source rectangle `extent` = (x0, y0, x1, y1), fractional, inside the frame or not, stretched over the output.  One
+    extent for all frames or one per frame.  Pillow turns it into the affine map of `extent_data` and nothing more, and so
+    does this: the work is `transform_frames`'s, whose arguments and result these are."""
+    who = 'extent_frames'
+    batches, _ = _batches(frames, who)
+    width, height = _size(size, who)
+    total = sum(b.shape[0] for b in batches)
+    try:
+        e = np.asarray(extent, np.float64)
+    except (TypeError, ValueError):
+        e = np.zeros(0)
+    if e.shape != (4,) and (total == 0 or e.shape != (total, 4)):
+        raise ValueError('%s: extent must be (x0, y0, x1, y1), or one for each of the %d frames' % (who, total))
+    if not np.isfinite(e).all():
+        raise ValueError('%s: extent must be finite' % who)
+    data = [extent_data((width, height), [float(v) for v in row]) for row in e.reshape(-1, 4)]
+    return transform_frames(frames, (width, height), lib.AFFINE, data[0] if e.ndim == 1 else data, resample, fillcolor, ctx)
+
+
+def _camera(matrix, what, who):
+    try:
+        k = np.asarray(matrix, np.float64)
+    except (TypeError, ValueError):
+        k = np.zeros(0)
+    if k.shape != (3, 3) or not np.isfinite(k).all() or k[0, 0] == 0 or k[1, 1] == 0:
+        raise ValueError('%s: %s must be a finite 3 x 3 matrix with non-zero focal lengths, got %r' % (who, what, matrix))
+    return k
+
+
+def undistort_cells(size, camera_matrix, dist_coeffs, grid=16, new_camera_matrix=None):
+    """The mesh that removes a lens's distortion from a size[0] x size[1] image, host only, numpy float64: a lattice
+    of `grid`-pixel cells over the OUTPUT (the last column and row narrower where the size is no multiple), each vertex
+    mapped to the source point the Brown-Conrady model gives it.  A vertex (u, v) -- a pixel CORNER in Pillow's
+    coordinates, (u - 0.5, v - 0.5) in the matrices', which put whole numbers at pixel centres -- is normalised with the
+    new matrix, y = (v - 0.5 - cy') / fy', x = (u - 0.5 - cx' - s' y) / fx'; distorted, with r2 = x x + y y and
+    radial = 1 + k1 r2 + k2 r2^2 + k3 r2^3,
+        xd = x radial + 2 p1 x y + p2 (r2 + 2 x x),  yd = y radial + p1 (r2 + 2 y y) + 2 p2 x y;
+    and projected with the camera matrix, (fx xd + s yd + cx + 0.5, fy yd + cy + 0.5).  `camera_matrix`: 3 x 3, rows
+    (fx, s, cx), (0, fy, cy), (0, 0, 1); `dist_coeffs`: (k1, k2, p1, p2) or (k1, k2, p1, p2, k3);
+    `new_camera_matrix`: the view wanted, default the camera's own.  Returns a lib.MESH_CELL_DT array, cells row by row,
+    as `pack_mesh` makes and `mesh_frames` takes; `undistort_mesh` is the same as Pillow's list."""
+    who = 'undistort_mesh'
+    width, height = _size(size, who)
+    k = _camera(camera_matrix, 'camera_matrix', who)
+    kn = k if new_camera_matrix is None else _camera(new_camera_matrix, 'new_camera_matrix', who)
+    try:
+        d = np.asarray(dist_coeffs, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        d = np.zeros(0)
+    if d.shape[0] not in (4, 5) or not np.isfinite(d).all():
+        raise ValueError('%s: dist_coeffs must be (k1, k2, p1, p2) or (k1, k2, p1, p2, k3), finite, got %r' % (who, dist_coeffs))
+    if not _is_int(grid) or not 1 <= grid <= lib.RESAMPLE_SIDE_LIMIT:
+        raise ValueError('%s: grid must be an int within 1 .. %d, got %r' % (who, lib.RESAMPLE_SIDE_LIMIT, grid))
+    grid = int(grid)
+    k1, k2, p1, p2 = d[:4]
+    k3 = d[4] if d.shape[0] == 5 else 0.0
+    xv = np.array(list(range(0, width, grid)) + [width], np.float64)
+    yv = np.array(list(range(0, height, grid)) + [height], np.float64)
+    if (len(xv) - 1) * (len(yv) - 1) > lib.MESH_MAX_CELLS:
+        raise ValueError('%s: a %d-pixel lattice over %d x %d has more than %d cells' % (who, grid, width, height, lib.MESH_MAX_CELLS))
+    with np.errstate(all='ignore'):                     # what overflows is refused below
+        y = ((yv - 0.5 - kn[1, 2]) / kn[1, 1])[:, None] + np.zeros((1, len(xv)))
+        x = (xv[None, :] - 0.5 - kn[0, 2] - kn[0, 1] * y) / kn[0, 0]
+        r2 = x * x + y * y
+        radial = 1 + k1 * r2 + k2 * r2 * r2 + k3 * r2 * r2 * r2
+        xd = x * radial + 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        yd = y * radial + p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        us = k[0, 0] * xd + k[0, 1] * yd + k[0, 2] + 0.5
+        vs = k[1, 1] * yd + k[1, 2] + 0.5
+    if not (np.isfinite(us).all() and np.isfinite(vs).all()):
+        raise ValueError('%s: the model leaves the finite numbers over this image' % who)
+    cells = np.zeros((len(yv) - 1, len(xv) - 1), lib.MESH_CELL_DT)
+    cells['x0'], cells['x1'] = xv[None, :-1], xv[None, 1:]
+    cells['y0'], cells['y1'] = yv[:-1, None], yv[1:, None]
+    cells['quad'] = np.stack([us[:-1, :-1], vs[:-1, :-1], us[1:, :-1], vs[1:, :-1], us[1:, 1:], vs[1:, 1:], us[:-1, 1:], vs[:-1, 1:]], -1)
+    return cells.reshape(-1)
+
+
+def undistort_mesh(size, camera_matrix, dist_coeffs, grid=16, new_camera_matrix=None):
+    """`undistort_cells` as the plain list Pillow takes: [((x0, y0, x1, y1), (8 floats: nw, sw, se, ne)), ...], cells row by
+    row, for `Image.transform(size, Image.MESH, ...)`, `ImageOps.deform` and `mesh_frames`.  Host only."""
+    cells = undistort_cells(size, camera_matrix, dist_coeffs, grid, new_camera_matrix)
+    return [((int(c['x0']), int(c['y0']), int(c['x1']), int(c['y1'])), tuple(float(v) for v in c['quad'])) for c in cells]
+
+
+def undistort_frames(frames, camera_matrix, dist_coeffs, grid=16, resample='bilinear', new_camera_matrix=None, fillcolor=None,
+                     ctx=None):
+    """Resident frames of a wide-angle or otherwise distorting camera made rectilinear -> one NEW batch of the same size:
+    `mesh_frames` with `undistort_mesh(frame size, camera_matrix, dist_coeffs, grid, new_camera_matrix)`, so all frames must
+    have one size.  The result is Pillow's MESH of that lattice, bit for bit: exact at the lattice's vertices and bilinear
+    in the source position within a cell.  It is NOT a per-pixel remap, and no parity with OpenCV's undistort is claimed; a
+    finer `grid` follows the model more closely at the cost of more cells."""
+    who = 'undistort_frames'
+    batches, _ = _batches(frames, who)
+    size = _mesh_size(batches, None, who)
+    cells = undistort_cells(size, camera_matrix, dist_coeffs, grid, new_camera_matrix)
+    return mesh_frames(frames, cells, size, resample, fillcolor, ctx)
 
 
 # ---- pixel values: histograms, statistics, look-up tables ---------------------------------------------------------------

@@ -58,6 +58,9 @@ SIGNATURES = {
     'ta_resample_plan': (c_int, [c_int, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_int, P(c_int)]),
     'ta_frames_pixelate': (c_int, [c_void_p, c_void_p, c_void_p, c_int]),
     'ta_frames_transform': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, P(c_void_p)]),
+    'ta_frames_transform_mesh': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_void_p, P(c_void_p)]),
+    'ta_mesh_plan': (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
     'ta_frames_transpose': (c_int, [c_void_p, c_void_p, c_int, P(c_void_p)]),
     'ta_frames_histogram': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_frames_point': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int]),
@@ -268,6 +271,38 @@ assert TRANSFORM_DT.itemsize == 72
 FLIP_LEFT_RIGHT, FLIP_TOP_BOTTOM, ROTATE_90, ROTATE_180, ROTATE_270, TRANSPOSE, TRANSVERSE = range(7)
 TRANSPOSE_OPS = {'flip_left_right': FLIP_LEFT_RIGHT, 'flip_top_bottom': FLIP_TOP_BOTTOM, 'rotate_90': ROTATE_90,
                  'rotate_180': ROTATE_180, 'rotate_270': ROTATE_270, 'transpose': TRANSPOSE, 'transverse': TRANSVERSE}
+
+
+# ta_mesh_cell, ta_mesh_image (include/terran_amd.h): a cell's half-open box of the OUTPUT and its quadrilateral of the INPUT
+# in Pillow's corner order nw, sw, se, ne; an output image's source frame and mesh.  TA_MESH_*: the tile and the limits
+MESH_CELL_DT = np.dtype([('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('quad', '<f8', (8,))])
+assert MESH_CELL_DT.itemsize == 80
+MESH_IMAGE_DT = np.dtype([('frame', '<i4'), ('mesh', '<i4')])
+assert MESH_IMAGE_DT.itemsize == 8
+MESH_TILE_W, MESH_TILE_H = 64, 16
+MESH_MAX_CELLS, MESH_MAX_ENTRIES = 1 << 20, 1 << 24
+MESH_COORD_LIMIT = 1 << 24
+
+
+def mesh_plan(cells, out_h, out_w):
+    """Host only (no context, no device): ta_mesh_plan -> (float64 (n, 8) coefficients a0 .. a7, int32 (n, 4) clamped boxes
+    cx0, cy0, cx1, cy1, int32 (tiles + 1,) tile_first, int32 tile_cells): what ta_frames_transform_mesh derives from ONE
+    mesh (a MESH_CELL_DT array) and an output size before it launches anything.  Tile t (row-major over the
+    MESH_TILE_W x MESH_TILE_H tiles of the output) holds the cells tile_cells[tile_first[t]:tile_first[t + 1]]."""
+    lib = load()
+    cells, p, n = _records(cells, MESH_CELL_DT)
+    out_h, out_w = int(out_h), int(out_w)
+    k = c_int()
+    rc = lib.ta_mesh_plan(p, n, out_h, out_w, None, None, None, None, -1, C.byref(k))
+    if rc != E_CAPACITY:
+        raise TerranAmdError(rc, 'mesh_plan: a bad output size, box or corner, or more cells or tile entries than the limits')
+    tiles = -(-out_w // MESH_TILE_W) * -(-out_h // MESH_TILE_H)
+    coefs, boxes = np.zeros((n, 8), np.float64), np.zeros((n, 4), np.int32)
+    first, entries = np.zeros(tiles + 1, np.int32), np.zeros(k.value, np.int32)
+    rc = lib.ta_mesh_plan(p, n, out_h, out_w, ptr(coefs), ptr(boxes), ptr(first), ptr(entries), k.value, C.byref(k))
+    if rc != OK:
+        raise TerranAmdError(rc, 'mesh_plan')
+    return coefs, boxes, first, entries
 
 
 def transpose_op(op):
@@ -780,6 +815,23 @@ class Frames:
         rgb = None if fill is None else np.array(fill, np.uint8).reshape(3)
         hd = c_void_p()
         ctx.check(ctx.lib.ta_frames_transform(ctx.h, self.h, p, n, int(out_h), int(out_w), int(filter), ptr(rgb), C.byref(hd)))
+        return Frames(ctx, handle=hd) if hd.value else None
+
+    def transform_mesh(self, cells, mesh_first, images, out_h, out_w, filter, fill=None, ctx=None):
+        """A NEW batch (len(images), out_h, out_w, 3): image i is Pillow's transform((out_w, out_h), MESH, cells of mesh
+        images[i]['mesh'], resample=filter, fillcolor=fill) of the frame images[i]['frame'] (ta_frames_transform_mesh), or
+        None without images.  `cells`: a MESH_CELL_DT array, the meshes one after the other; `mesh_first`: their n_meshes + 1
+        offsets into it; `images`: a MESH_IMAGE_DT array.  `filter`, `fill`, `ctx`: as in `transform`."""
+        ctx = ctx or self.ctx
+        cells, pc, nc = _records(cells, MESH_CELL_DT)
+        first = np.ascontiguousarray(mesh_first, dtype=np.int32).reshape(-1)
+        if len(first) < 1:
+            raise ValueError('transform_mesh: mesh_first must hold n_meshes + 1 offsets')
+        images, pi, ni = _records(images, MESH_IMAGE_DT)
+        rgb = None if fill is None else np.array(fill, np.uint8).reshape(3)
+        hd = c_void_p()
+        ctx.check(ctx.lib.ta_frames_transform_mesh(ctx.h, self.h, pc, nc, ptr(first), len(first) - 1, pi, ni, int(out_h), int(out_w),
+                                                   int(filter), ptr(rgb), C.byref(hd)))
         return Frames(ctx, handle=hd) if hd.value else None
 
     def transpose(self, op, ctx=None):

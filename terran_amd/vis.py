@@ -30,7 +30,8 @@ take as it is.
 Host glue only: the packing of results into primitives is numpy; the drawing is one ta_frames_draw(_masks) launch, the
 blurring one ta_frames_blur or ta_frames_pixelate call, the cropping one ta_frames_resample call, the aligned chips of
 `align_faces` (the embedder's five-point similarity, Pillow's Image.transform; csrc/transform.hip) one ta_frames_transform
-call.  Importing this module needs no GPU and no Pillow.
+call, the upright chips `quad_chips` cuts out of quadrilaterals (Pillow's Image.QUAD) one ta_frames_transform_mesh call.
+Importing this module needs no GPU and no Pillow.
 """
 import collections
 import math
@@ -519,6 +520,54 @@ def align_faces(frames, faces_per_frame, size=(112, 112), resample='bilinear', c
     if not len(regions):
         return None, []
     return frames.transform(regions, height, width, code, ctx=ctx), index
+
+
+def pack_quads(quads_per_frame, size):
+    """-> (lib.MESH_CELL_DT array, lib.MESH_IMAGE_DT array, int32 (n, 2) index of (frame, quad) pairs): for every quad, in
+    order, frame by frame, the one-cell mesh ((0, 0) + size, quad) of its chip and the frame it is cut from; mesh k is cell
+    k.  A quad is 8 finite numbers, the corners nw, sw, se, ne as (x, y) in its frame.  Host only."""
+    width, height = _chip_size(size)
+    quads, index = [], []
+    for f, per in enumerate(quads_per_frame):
+        try:
+            per = np.asarray(per, np.float64)
+        except (TypeError, ValueError):
+            per = np.zeros(1)
+        if per.size == 0:
+            per = np.zeros((0, 8))
+        elif per.shape == (8,):                             # a single quad for this frame
+            per = per[None]
+        if per.ndim != 2 or per.shape[1] != 8 or not np.isfinite(per).all():
+            raise ValueError('quad_chips: the quads of frame %d must be 8 finite numbers each' % f)
+        quads.extend(per)
+        index.extend((f, k) for k in range(len(per)))
+    cells = np.zeros(len(quads), lib.MESH_CELL_DT)
+    images = np.zeros(len(quads), lib.MESH_IMAGE_DT)
+    if quads:
+        cells['x1'], cells['y1'], cells['quad'] = width, height, np.stack(quads)
+        images['frame'], images['mesh'] = [f for f, _ in index], np.arange(len(quads))
+    return cells, images, np.array(index, np.int32).reshape(-1, 2)
+
+
+def quad_chips(frames, quads_per_frame, size, resample='bilinear', ctx=None):
+    """Cut quadrilaterals -- screens, whiteboards, plates, given by their four corners -- out of the resident batch `frames`
+    (lib.Frames) as upright chips of one size -> (chips, index) as `crop_faces` returns them: `chips` one resident
+    (n_quads, height, width, 3) lib.Frames (None when there is no quad), each Pillow's
+    `Image.fromarray(frame).transform(size, Image.QUAD, quad, resample)`; `index` the int32 (n_quads, 2) (frame, quad) pairs.
+    quads_per_frame[i]: the quads of frame i, 8 numbers each (nw, sw, se, ne; x, y).  One ta_frames_transform_mesh call
+    for all quads of all frames, one single-cell mesh per chip.  `size`: (width, height); `resample`: 'nearest',
+    'bilinear', 'bicubic' or Pillow's code."""
+    _check_batch(frames, quads_per_frame)
+    width, height = _chip_size(size)
+    code = lib.resample_filter(resample)
+    if code not in lib.TRANSFORM_FILTERS:
+        raise ValueError("quad_chips: resample must be 'nearest', 'bilinear' or 'bicubic', got %r" % (resample,))
+    cells, images, index = pack_quads(quads_per_frame, size)
+    if not len(cells):
+        return None, []
+    if len(cells) > lib.MESH_MAX_CELLS:
+        raise ValueError('quad_chips: more than %d quads' % lib.MESH_MAX_CELLS)
+    return frames.transform_mesh(cells, np.arange(len(cells) + 1), images, height, width, code, ctx=ctx), index
 
 
 def _chip_size(size):
