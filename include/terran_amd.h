@@ -422,6 +422,55 @@ int ta_frames_color(ta_ctx* ctx, ta_frames* frames, const ta_color_region* regio
 int ta_color_plan(const ta_color_region* regions, int n, const ta_color_op* ops, int n_ops, const float* tables, size_t n_tables,
                   int32_t* rounds, int16_t* nodes);
 
+/* ---- raw YUV video frames: yuv420p, nv12, yuv444p in and out --------------------------------- */
+/* Frames as `ffmpeg -f rawvideo -pix_fmt yuv420p | nv12 | yuv444p` lays them out, back to back without padding, with
+ * cw = (w + 1) >> 1 and ch = (h + 1) >> 1:
+ *     TA_YUV_420P   Y h x w, U ch x cw, V ch x cw         w h + 2 cw ch bytes (may be odd: a frame starts at any address)
+ *     TA_YUV_NV12   Y h x w, ch rows of cw (U, V) pairs   the same size
+ *     TA_YUV_444P   Y, U, V, each h x w                   3 w h bytes
+ * The conversion is the standards' affine map with exact rational coefficients, rounded once, half up -- NOT swscale's
+ * tables; no parity with ffmpeg's own converter is claimed.  Kr, Kb = 299/1000, 114/1000 (TA_YUV_BT601) or 2126/10000,
+ * 722/10000 (TA_YUV_BT709), Kg = 1 - Kr - Kb.
+ *   YUV -> RGB: y' = (Y - 16) / 219, c' = (C - 128) / 224 (TA_YUV_TV) or Y / 255, (C - 128) / 255 (TA_YUV_PC);
+ *     R' = y' + 2 (1 - Kr) cr', B' = y' + 2 (1 - Kb) cb', G' = y' - (2 Kr (1 - Kr) / Kg) cr' - (2 Kb (1 - Kb) / Kg) cb';
+ *     every output is clip(floor(255 X' + 1/2), 0, 255), also for inputs outside the nominal range.
+ *     The chroma of pixel (x, y) of a 4:2:0 format is an 8-bit value, every index clamped to the plane:
+ *     TA_YUV_NEAREST: C[y >> 1][x >> 1].  TA_YUV_BILINEAR: vertically 3 C[j] + C[j - 1] for y = 2 j and 3 C[j] + C[j + 1] for
+ *     y = 2 j + 1; horizontally with TA_YUV_LEFT (MPEG-2, H.264) 2 C[x / 2] for even x and C[i] + C[i + 1], i = (x - 1) / 2,
+ *     for odd x, the value (sum + 4) >> 3; with TA_YUV_CENTER (JPEG, MPEG-1) the 3 : 1 rule again, (sum + 8) >> 4.
+ *   RGB -> YUV: L = Kr R + Kg G + Kb B; TV: Y = 16 + 219 L / 255, Cb = 128 + 224 (B - L) / (255 * 2 (1 - Kb)), Cr likewise
+ *     with R and Kr; PC: Y = L, Cb = 128 + (B - L) / (2 (1 - Kb)); each clip(floor(v + 1/2), 0, 255).  In a 4:2:0 format
+ *     Cb and Cr come from the exact mean of R, G, B over the pixels of the 2 x 2 block that lie inside the frame, rounded
+ *     once; `chroma` and `siting` are checked but not used in this direction, nor by TA_YUV_444P in either.
+ * ta_frames_from_yuv copies n frames from `host_yuv` (pinned or pageable) into a grow-only staging block of the context
+ * that no other call uses and converts them into a NEW batch in one launch; ta_frames_to_yuv converts a batch into the
+ * context's scratch block in one launch and copies the n frames to `host_yuv`.  Both run on `ctx`'s stream and return when
+ * they are done.  A video reader's thread may therefore call ta_frames_from_yuv on its own context while another thread
+ * runs the other frame calls on that context's batches, as it may with ta_frames_upload.
+ * TA_E_INVALID, before any launch and with *out untouched: a null pointer, an unknown value of a spec field, n, h or w
+ * below 1, a side above 65535, a batch of another device. */
+#define TA_YUV_420P 0
+#define TA_YUV_NV12 1
+#define TA_YUV_444P 2
+#define TA_YUV_BT601 0
+#define TA_YUV_BT709 1
+#define TA_YUV_TV 0
+#define TA_YUV_PC 1
+#define TA_YUV_NEAREST 0
+#define TA_YUV_BILINEAR 1
+#define TA_YUV_LEFT 0
+#define TA_YUV_CENTER 1
+typedef struct ta_yuv_spec {
+  int32_t format, matrix, range, chroma, siting;
+} ta_yuv_spec;
+/* HOST ONLY: the bytes of one frame; 0 for an unknown format or a side outside 1 .. 65535 */
+size_t ta_yuv_frame_bytes(int format, int h, int w);
+int ta_frames_from_yuv(ta_ctx* ctx, const uint8_t* host_yuv, int n, int h, int w, const ta_yuv_spec* spec, ta_frames** out);
+int ta_frames_to_yuv(ta_ctx* ctx, const ta_frames* frames, const ta_yuv_spec* spec, uint8_t* host_yuv);
+/* HOST ONLY, no context: n triples through the arithmetic the kernels run.  to_yuv = 0: (Y, Cb, Cr) -> (R, G, B);
+ * 1: (R, G, B) -> (Y, Cb, Cr) of a single pixel.  in3 and out3 may be the same array. */
+int ta_yuv_convert_samples(const ta_yuv_spec* spec, int to_yuv, const uint8_t* in3, size_t n, uint8_t* out3);
+
 /* ---- neighbourhood filters: convolution kernels, rank filters, unsharp mask ----------------- */
 /* Filters regions of `frames` in place, Pillow's
  *     im.paste(im.crop(box).filter(F), box[, ellipse mask])

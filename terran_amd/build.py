@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libterran_amd.so')
 SOURCES = ['runtime.hip', 'frames.hip', 'conv_split.hip', 'conv_split_modes.hip', 'conv_sym.hip', 'conv_dwpw.hip', 'conv_igemm.hip', 'layers.hip', 'model_load.hip', 'model_plan.hip', 'model_run.hip', 'retinaface_post.hip', 'arcface_post.hip',
-           'openpose_post.hip', 'draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip', 'combine.hip', 'color.hip', 'jpeg_host.hip', 'jpeg.hip',
+           'openpose_post.hip', 'draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip', 'combine.hip', 'color.hip', 'yuv.hip', 'jpeg_host.hip', 'jpeg.hip',
            'jpeg_encode.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 

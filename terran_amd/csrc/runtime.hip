@@ -192,6 +192,7 @@ void ta_ctx_destroy(ta_ctx* ctx) {
   if (ctx->pose_wphase) (void)hipFree(ctx->pose_wphase);
   if (ctx->jpeg_enc_dev) (void)hipFree(ctx->jpeg_enc_dev);
   if (ctx->jpeg_enc_out) (void)hipHostFree(ctx->jpeg_enc_out);
+  if (ctx->yuv_in) (void)hipFree(ctx->yuv_in);
   ta_pose_free_big(ctx);
   if (ctx->range_flag) (void)hipFree(ctx->range_flag);
   if (ctx->range_flag_host) (void)hipHostFree(ctx->range_flag_host);

@@ -137,6 +137,11 @@ struct ta_ctx {
   size_t jpeg_enc_dev_bytes = 0;
   uint8_t* jpeg_enc_out = nullptr;                 // pinned: the files of the last ta_jpeg_encode, grow-only
   size_t jpeg_enc_out_bytes = 0;
+  // ta_frames_from_yuv's staging block (device, grow-only) and nothing else's: a video reader's thread converts on its own
+  // context while the consumer's calls on that context's batches (draw, encode, to_yuv) use `scratch`, so the two never
+  // share a block; only one thread at a time calls ta_frames_from_yuv on a context
+  void* yuv_in = nullptr;
+  size_t yuv_in_bytes = 0;
   float* pose_wphase = nullptr;                    // x8 bicubic phase weights on the device (uploaded once per context)
   // where the last grouping left its per-stage results in the scratch block (ta_openpose_debug_read); n = 0: none
   struct {

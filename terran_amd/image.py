@@ -49,6 +49,12 @@ Colour: `convert_frames` ('YCbCr', 'HSV' and back, or 'RGB' with a matrix), `mat
 (`ImageFilter.Color3DLUT`) and `hue_frames` are Pillow's `Image.convert` and 3-D table filter on resident frames
 (`ta_frames_color`), in place and bit for bit; `color_spec` builds their op records without a device.  A batch has no
 mode: after a conversion its three bytes per pixel are Y, Cb, Cr or H, S, V, and the caller keeps track of that.
+
+Raw video: `frames_from_yuv` / `frames_to_yuv` convert between raw `yuv420p`, `nv12` or `yuv444p` frames (ffmpeg's
+`-f rawvideo` layout) and resident RGB batches on the GPU (`ta_frames_from_yuv`, `ta_frames_to_yuv`).  The conversion is
+the standards' affine map (BT.601 or BT.709, tv or pc range) with exact rational coefficients, rounded once, half up;
+it is NOT bit for bit what ffmpeg's swscale computes, and no such parity is claimed.  `yuv_spec` and `yuv_frame_bytes`
+work without a device.
 """
 import os
 from pathlib import Path
@@ -1563,3 +1569,105 @@ def save_images(images, paths, quality=75, subsampling=-1, ctx=None, device=None
     for data, path in zip(files, paths):
         with open(_path(path), 'wb') as fh:
             fh.write(data)
+
+
+# ---- raw YUV video frames --------------------------------------------------------------------------------------------
+def _yuv_choice(value, table, what):
+    if not isinstance(value, str) or value not in table:
+        raise ValueError('yuv_spec: %s must be one of %s, got %r' % (what, ', '.join(repr(k) for k in table), value))
+    return table[value]
+
+
+def yuv_spec(pix_fmt, matrix='bt709', range='tv', chroma='bilinear', siting='left'):
+    """The lib.YUV_SPEC_DT record of a raw YUV conversion; ValueError names the argument that is wrong.
+    pix_fmt: 'yuv420p', 'nv12' or 'yuv444p'.  matrix: 'bt601' or 'bt709'.  range: 'tv' (16 .. 235 / 240) or 'pc' (0 .. 255).
+    chroma: how a 4:2:0 format's chroma is brought to every pixel on the way IN, 'nearest' or 'bilinear'; siting: where its
+    samples sit horizontally, 'left' (MPEG-2, H.264) or 'center' (JPEG, MPEG-1).  On the way OUT (frames_to_yuv) a chroma
+    sample is the conversion of its block's mean, and `chroma` and `siting` are checked but not used; yuv444p uses neither."""
+    return np.array((_yuv_choice(pix_fmt, lib.YUV_FORMATS, 'pix_fmt'), _yuv_choice(matrix, lib.YUV_MATRICES, 'matrix'),
+                     _yuv_choice(range, lib.YUV_RANGES, 'range'), _yuv_choice(chroma, lib.YUV_CHROMAS, 'chroma'),
+                     _yuv_choice(siting, lib.YUV_SITINGS, 'siting')), dtype=lib.YUV_SPEC_DT)
+
+
+def _yuv_size(size, who):
+    try:
+        width, height = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError('%s: size must be (width, height), got %r' % (who, size)) from None
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError('%s: size must be within 1 .. 65535 a side, got %r' % (who, size))
+    return width, height
+
+
+def yuv_frame_bytes(pix_fmt, size):
+    """The bytes of one raw frame of `size` = (width, height): w h + 2 ((w + 1) >> 1) ((h + 1) >> 1) for 'yuv420p' and
+    'nv12', 3 w h for 'yuv444p'.  Host only."""
+    code = _yuv_choice(pix_fmt, lib.YUV_FORMATS, 'pix_fmt')
+    width, height = _yuv_size(size, 'yuv_frame_bytes')
+    return lib.yuv_frame_bytes(code, height, width)
+
+
+def frames_from_yuv(data, size, pix_fmt='yuv420p', matrix='bt709', range='tv', chroma='bilinear', siting='left', ctx=None,
+                    device=None):
+    """Raw YUV frames -> ONE resident RGB batch (ta_frames_from_yuv).  `data`: bytes or a uint8 array of whole frames of
+    `size` = (width, height), back to back as `ffmpeg -f rawvideo -pix_fmt <pix_fmt>` writes them.  The other arguments
+    are yuv_spec's."""
+    spec = yuv_spec(pix_fmt, matrix, range, chroma, siting)
+    width, height = _yuv_size(size, 'frames_from_yuv')
+    per = lib.yuv_frame_bytes(spec['format'], height, width)
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        arr = np.frombuffer(data, np.uint8)
+    else:
+        arr = np.asarray(data)
+        if arr.dtype != np.uint8:
+            raise ValueError('frames_from_yuv: data must be bytes or a uint8 array, got %s' % arr.dtype)
+        arr = np.ascontiguousarray(arr).reshape(-1)
+    if arr.size == 0 or arr.size % per:
+        raise ValueError('frames_from_yuv: %d bytes are not whole %s frames of %d x %d (%d bytes each)'
+                         % (arr.size, pix_fmt, width, height, per))
+    ctx = ctx if ctx is not None else runtime.get_context(device)
+    return ctx.frames_from_yuv(arr, arr.size // per, height, width, spec)
+
+
+def frames_to_yuv(frames, pix_fmt='yuv420p', matrix='bt709', range='tv', chroma='bilinear', siting='left', ctx=None, device=None):
+    """Resident frames -> raw YUV frames, a uint8 (n, frame_bytes) array in frame order (ta_frames_to_yuv): written to a
+    file or a pipe as it is, it is what `ffmpeg -f rawvideo -pix_fmt <pix_fmt> -s WxH -i pipe:` reads.  `frames`: what
+    encode_jpeg accepts -- a `lib.Frames` batch, a list of them (all of one size), or a host uint8 (H, W, 3) / (N, H, W, 3)
+    array (uploaded first).  A 4:2:0 chroma sample is the conversion of the mean of its block; `chroma` and `siting` are
+    checked but not used in this direction.  The conversion runs on `ctx`, by default the CALLING thread's context of the
+    batch's device (runtime.get_context) and never the batch's own: a batch from a video reader belongs to the reader
+    thread's context, which that thread is using."""
+    spec = yuv_spec(pix_fmt, matrix, range, chroma, siting)
+    if isinstance(frames, lib.Frames):
+        batches = [frames]
+    elif isinstance(frames, (list, tuple)):
+        batches = list(frames)
+        if not batches or not all(isinstance(b, lib.Frames) for b in batches):
+            raise ValueError('frames_to_yuv: a list must hold lib.Frames batches')
+        if len({b.shape[1:3] for b in batches}) != 1:
+            raise ValueError('frames_to_yuv: the batches of a list must have one frame size')
+    else:
+        arr = np.asarray(frames)
+        if arr.dtype != np.uint8 or arr.ndim not in (3, 4) or arr.shape[-1] != 3 or 0 in arr.shape:
+            raise ValueError('frames_to_yuv: host images must be uint8 (H, W, 3) or (N, H, W, 3) RGB, got %s %s'
+                             % (arr.dtype, arr.shape))
+        _yuv_size(arr.shape[-2:-4:-1], 'frames_to_yuv')
+        ctx = ctx if ctx is not None else runtime.get_context(device)
+        up = ctx.upload(arr[None] if arr.ndim == 3 else arr)
+        try:
+            return up.to_yuv(spec, ctx=ctx)
+        finally:
+            up.free()
+    for b in batches:
+        _yuv_size(b.shape[2:0:-1], 'frames_to_yuv')
+    if ctx is None:
+        ctx = runtime.get_context(device if device is not None else batches[0].ctx.device_id)
+    if len(batches) == 1:
+        return batches[0].to_yuv(spec, ctx=ctx)
+    per = lib.yuv_frame_bytes(spec['format'], batches[0].shape[1], batches[0].shape[2])
+    out = np.empty((sum(b.shape[0] for b in batches), per), np.uint8)
+    at = 0
+    for b in batches:
+        b.to_yuv(spec, out=out[at:at + b.shape[0]], ctx=ctx)
+        at += b.shape[0]
+    return out

@@ -69,6 +69,10 @@ SIGNATURES = {
     'ta_filter_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     'ta_frames_color': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_color_plan': (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    'ta_yuv_frame_bytes': (c_size_t, [c_int, c_int, c_int]),
+    'ta_frames_from_yuv': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, P(c_void_p)]),
+    'ta_frames_to_yuv': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    'ta_yuv_convert_samples': (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'ta_frames_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
@@ -219,6 +223,47 @@ def color_plan(regions, ops, tables=None):
         out.append(nodes[at:at + 4 * c].reshape(int(o['size'][2]), int(o['size'][1]), int(o['size'][0]), 4) if c else None)
         at += 4 * c
     return rounds, out
+
+
+# ta_yuv_spec (include/terran_amd.h) and the values of its fields, TA_YUV_*
+YUV_420P, YUV_NV12, YUV_444P = 0, 1, 2
+YUV_BT601, YUV_BT709 = 0, 1
+YUV_TV, YUV_PC = 0, 1
+YUV_NEAREST, YUV_BILINEAR = 0, 1
+YUV_LEFT, YUV_CENTER = 0, 1
+YUV_FORMATS = {'yuv420p': YUV_420P, 'nv12': YUV_NV12, 'yuv444p': YUV_444P}
+YUV_MATRICES = {'bt601': YUV_BT601, 'bt709': YUV_BT709}
+YUV_RANGES = {'tv': YUV_TV, 'pc': YUV_PC}
+YUV_CHROMAS = {'nearest': YUV_NEAREST, 'bilinear': YUV_BILINEAR}
+YUV_SITINGS = {'left': YUV_LEFT, 'center': YUV_CENTER}
+YUV_SPEC_DT = np.dtype([('format', '<i4'), ('matrix', '<i4'), ('range', '<i4'), ('chroma', '<i4'), ('siting', '<i4')])
+assert YUV_SPEC_DT.itemsize == 20
+
+
+def _yuv_spec(spec):
+    """One ta_yuv_spec record: a YUV_SPEC_DT record or five integers (format, matrix, range, chroma, siting)."""
+    if isinstance(spec, np.ndarray) and spec.dtype == YUV_SPEC_DT:
+        return np.ascontiguousarray(spec).reshape(1)
+    return np.array([tuple(int(v) for v in spec)], dtype=YUV_SPEC_DT)
+
+
+def yuv_frame_bytes(format, h, w):
+    """Host only: ta_yuv_frame_bytes, the bytes of one h x w frame; 0 for an unknown format or a side outside 1 .. 65535."""
+    return int(load().ta_yuv_frame_bytes(int(format), int(h), int(w)))
+
+
+def yuv_convert_samples(spec, to_yuv, triples):
+    """Host only (no context, no device): ta_yuv_convert_samples, (n, 3) uint8 triples through the arithmetic the kernels
+    run -- (Y, Cb, Cr) -> (R, G, B), or with to_yuv (R, G, B) -> (Y, Cb, Cr) of a single pixel."""
+    src = np.ascontiguousarray(triples, dtype=np.uint8)
+    if src.ndim != 2 or src.shape[1] != 3:
+        raise ValueError('yuv_convert_samples: triples must be (n, 3) uint8, got %s' % (src.shape,))
+    s = _yuv_spec(spec)
+    out = np.empty_like(src)
+    rc = load().ta_yuv_convert_samples(ptr(s), int(bool(to_yuv)), ptr(src), len(src), ptr(out))
+    if rc != OK:
+        raise TerranAmdError(rc, 'yuv_convert_samples: invalid spec')
+    return out
 
 
 def filter_plan(regions, specs):
@@ -526,6 +571,21 @@ class Context:
         images = np.ascontiguousarray(images, dtype=np.uint8)
         assert images.ndim == 4 and images.shape[3] == 3
         return Frames(self, images)
+
+    def frames_from_yuv(self, data, n, h, w, spec):
+        """ta_frames_from_yuv: `data`, a contiguous uint8 array of exactly n raw YUV frames of h x w (pinned or not), ->
+        a NEW resident Frames batch.  `spec`: a YUV_SPEC_DT record (image.yuv_spec)."""
+        s = _yuv_spec(spec)
+        if not (isinstance(data, np.ndarray) and data.dtype == np.uint8 and data.flags['C_CONTIGUOUS']):
+            data = np.ascontiguousarray(np.frombuffer(data, np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else data,
+                                        dtype=np.uint8)
+        n, h, w = int(n), int(h), int(w)
+        per = yuv_frame_bytes(s['format'][0], h, w)
+        if per and n > 0 and data.size != n * per:
+            raise ValueError('frames_from_yuv: %d bytes are not %d frames of %d bytes' % (data.size, n, per))
+        hd = c_void_p()
+        self.check(self.lib.ta_frames_from_yuv(self.h, ptr(data), n, h, w, ptr(s), C.byref(hd)))
+        return Frames(self, handle=hd)
 
     def pinned_array(self, shape):
         """uint8 numpy array backed by page-locked host memory (freed with `free_pinned`)."""
@@ -846,6 +906,20 @@ class Frames:
         """This batch as JPEG files (list of bytes, Pillow's for the same options).  `ctx`: the context the encode runs
         on -- the CALLER's, as in `draw`, so it is ordered after a draw on that context."""
         return (ctx or self.ctx).jpeg_encode(self, quality, subsampling, optimize)
+
+    def to_yuv(self, spec, out=None, ctx=None):
+        """ta_frames_to_yuv: this batch as raw YUV frames, a uint8 (n, frame_bytes) array (`out`, if given: contiguous and
+        of that shape).  `ctx`: the context the conversion runs on -- the CALLER's, as in `draw`."""
+        ctx = ctx or self.ctx
+        s = _yuv_spec(spec)
+        per = yuv_frame_bytes(s['format'][0], self.shape[1], self.shape[2])
+        if out is None:
+            out = np.empty((self.shape[0], max(per, 1)), np.uint8)
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.uint8 and out.flags['C_CONTIGUOUS'] and per
+                  and out.shape == (self.shape[0], per)):
+            raise ValueError('to_yuv: out must be a contiguous uint8 array of shape (%d, %d)' % (self.shape[0], per))
+        ctx.check(ctx.lib.ta_frames_to_yuv(ctx.h, self.h, ptr(s), ptr(out)))
+        return out
 
     def download(self):
         out = np.empty(self.shape, np.uint8)
