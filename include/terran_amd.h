@@ -789,6 +789,10 @@ int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connectio
 int ta_openpose_debug_read(ta_ctx* ctx, int n, int cap_peaks, int32_t* peak_counts, int32_t* peaks_yx,
                            float* peak_scores, int cap_conn, int32_t* conn_counts, int32_t* conn_ij,
                            float* conn_scores);
+/* Which work area those taps come from: peak_capacity (n,) int32 = rows per part of image i's lists.  1024 for an
+ * image the batch pass kept; an image that outgrew a list and was re-run alone reports the capacity its re-run was
+ * sized to (its largest peak count of one part). */
+int ta_openpose_debug_capacity(ta_ctx* ctx, int n, int32_t* peak_capacity);
 
 /* x8 bicubic upsample alone (wrapper.py:214-223): maps (N,C,h,w) -> (N,C,8h,8w). */
 int ta_bicubic_x8(ta_ctx* ctx, const float* maps, int n, int c, int h, int w, float* out);

@@ -198,12 +198,23 @@ def assemble_humans(peaks, connections_per_limb, debug=None):
     (limb missing: an endpoint part has no peaks) or list of (i, j, score).
     Returns (peaks_by_id (P,3) float64 [y,x,score], humans (M,20) float64).
     debug: a dict that receives `unfiltered`, the humans before the final filter
-    (tests/margins.py: how far each was from the 0.4 bar)."""
+    (tests/margins.py: how far each was from the 0.4 bar), and `events`, which
+    branch every connection took (tests/pose_crowd.py):
+      created / extended / present / merged / overlap / multi / late : counts of
+          connections that made a human, extended the one they hit, found their
+          destination already there (`hm[kd] == b`), merged two humans, extended
+          the first of two overlapping humans, hit three or more humans (ignored)
+          and, on limbs 17 / 18, hit none (ignored)
+      merges     : per merge (hit[0], hit[1], len(humans) before the delete)
+      max_humans : the largest len(humans) reached
+      cut_count / cut_score : rows the final filter removed for `count < 4` /
+          (of the others) for `score / count < 0.4`"""
     offs = np.cumsum([0] + [p[0].shape[0] for p in peaks])
     rows = [(float(y), float(x), float(s)) for locs, scs in peaks for (y, x), s in zip(locs, scs)]
     peaks_by_id = np.array(rows, dtype=np.float64).reshape(-1, 3)
 
     humans = []       # each: np.float64 (20,): 18 peak ids (-1 absent), [18]=score sum, [19]=count
+    ev = dict(created=0, extended=0, present=0, merged=0, overlap=0, multi=0, late=0, merges=[], max_humans=0)
     for limb_id in range(19):
         conns = connections_per_limb[limb_id]
         if conns is None:
@@ -216,6 +227,7 @@ def assemble_humans(peaks, connections_per_limb, debug=None):
             hit = [h for h in range(len(humans)) if humans[h][ks] == a or humans[h][kd] == b]
             if len(hit) == 1:
                 hm = humans[hit[0]]
+                ev['extended' if hm[kd] != b else 'present'] += 1
                 if hm[kd] != b:
                     hm[kd] = b
                     hm[19] += 1
@@ -223,7 +235,9 @@ def assemble_humans(peaks, connections_per_limb, debug=None):
             elif len(hit) == 2:
                 h1, h2 = humans[hit[0]], humans[hit[1]]
                 overlap = np.any((h1[:18] >= 0) & (h2[:18] >= 0))
+                ev['overlap' if overlap else 'merged'] += 1
                 if not overlap:
+                    ev['merges'].append((hit[0], hit[1], len(humans)))
                     h1[:18] += h2[:18] + 1
                     h1[18:] += h2[18:]
                     h1[18] += s
@@ -238,8 +252,17 @@ def assemble_humans(peaks, connections_per_limb, debug=None):
                 hm[19] = 2
                 hm[18] = (0 + peaks_by_id[int(a), 2] + peaks_by_id[int(b), 2]) + s
                 humans.append(hm)
+                ev['created'] += 1
+                ev['max_humans'] = max(ev['max_humans'], len(humans))
+            elif len(hit) == 0:
+                ev['late'] += 1
+            else:
+                ev['multi'] += 1
     if debug is not None:
         debug['unfiltered'] = [h.copy() for h in humans]
+        ev['cut_count'] = sum(1 for h in humans if h[19] < 4)
+        ev['cut_score'] = sum(1 for h in humans if not h[19] < 4 and h[18] / h[19] < HUMAN_THRESHOLD)
+        debug['events'] = ev
     kept = [h for h in humans if not (h[19] < 4 or h[18] / h[19] < HUMAN_THRESHOLD)]
     humans = np.array(kept, dtype=np.float64).reshape(-1, 20)
     return peaks_by_id, humans
@@ -261,19 +284,22 @@ def keypoints_out(peaks_by_id, humans, scale):
 def group_image(heatmaps_up, pafs_up, scale, debug=None):
     """Per-image tail on UPSAMPLED maps: (19,H,W), (38,H,W) -> list of dicts."""
     peaks = find_peaks(heatmaps_up)
-    conns = []
+    conns, pairs = [], []
     for limb_id in range(19):
         ks, kd = LIMBSEQ[limb_id][0] - 1, LIMBSEQ[limb_id][1] - 1
         ls, ld = peaks[ks][0], peaks[kd][0]
         if ls.shape[0] == 0 or ld.shape[0] == 0:
             conns.append(None)
+            pairs.append(0)
             continue
         reg, acc = score_limb(pafs_up, limb_id, ls, ld)
         conns.append(greedy_match(reg, acc))
-    peaks_by_id, humans = assemble_humans(peaks, conns)
+        pairs.append(int(acc.sum()))
+    peaks_by_id, humans = assemble_humans(peaks, conns, debug)
     if debug is not None:
         debug['peaks'] = peaks
         debug['connections'] = conns
+        debug['accepted_pairs'] = pairs       # per limb: candidate pairs score_limb accepted, before the matching
         debug['humans'] = humans
     return keypoints_out(peaks_by_id, humans, scale)
 

@@ -1095,6 +1095,19 @@ int ta_openpose_debug_read(ta_ctx* ctx, int n, int cap_peaks, int32_t* peak_coun
   return TA_OK;
 }
 
+int ta_openpose_debug_capacity(ta_ctx* ctx, int n, int32_t* peak_capacity) {
+  ta_enter(ctx);
+  if (!ctx || n <= 0 || !peak_capacity) return TA_E_INVALID;
+  const auto& d = ctx->pose_dbg;
+  if (d.n != n || !d.peak_cnt) return ta_fail(ctx, TA_E_INVALID, "openpose_debug_capacity: the last grouping on this context had %d images, not %d", d.n, n);
+  for (int img = 0; img < n; ++img) {
+    peak_capacity[img] = d.maxp;
+    for (const auto& o : d.over)
+      if (o.img == img && o.peak_cnt) peak_capacity[img] = o.maxp;
+  }
+  return TA_OK;
+}
+
 int ta_bicubic_x8(ta_ctx* ctx, const float* maps, int n, int c, int h, int w, float* out) {
   ta_enter(ctx);
   if (!ctx || n < 0 || c <= 0 || h <= 0 || w <= 0) return TA_E_INVALID;

@@ -111,6 +111,7 @@ SIGNATURES = {
     'ta_openpose_last_stats': (c_int, [c_void_p, c_void_p, c_void_p]),
     'ta_openpose_debug_read': (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p]),
+    'ta_openpose_debug_capacity': (c_int, [c_void_p, c_int, c_void_p]),
     'ta_debug_conv_variant': (c_int, [c_void_p, c_int]),
     'ta_debug_range_check': (c_int, [c_void_p]),
     'ta_debug_conv_counts': (c_int, [c_void_p, c_void_p, c_int]),
@@ -705,6 +706,13 @@ class Context:
         conns = [[None if cc[i, l] < 0 else (cij[i, l, :cc[i, l]].copy(), csc[i, l, :cc[i, l]].copy())
                   for l in range(19)] for i in range(n)]
         return peaks, conns
+
+    def pose_debug_capacity(self, n):
+        """Debug: rows per part of the work area each image's `pose_debug` taps come from -> [n] ints: 1024 for an image
+        the batch pass kept, its own largest peak count for an image that was re-run alone with larger lists."""
+        cap = np.zeros(n, np.int32)
+        self.check(self.lib.ta_openpose_debug_capacity(self.h, n, ptr(cap)))
+        return cap.tolist()
 
     def pose_stats(self):
         """(peaks, limb connections) of the last OpenPose grouping run on this context."""
