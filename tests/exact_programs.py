@@ -556,13 +556,41 @@ def convpool_net(precision, seed=4):
     return net
 
 
+def cover_inputs(rng, W, values):
+    """1x1 weights W (cout, C, 1, 1), in place: every input channel that no output row drew gets ONE weight of `values`, the idle
+    channels dealt round the rows in a random order (at most ceil(idle / cout) more per row).  What was drawn before stays."""
+    cout = W.shape[0]
+    idle = np.flatnonzero(~W[:, :, 0, 0].any(axis=0))
+    rows = rng.permutation(cout)
+    for i, c in enumerate(idle):
+        W[rows[i % cout], c, 0, 0] = rng.choice(values)
+    return W
+
+
 def dwpw_net(precision, C, cout, stride, seed=5):
-    """selector (3 -> C) -> 'src' (float32: the block reads nothing else) -> [dw 3x3 + ReLU -> 1x1 + ReLU] -> 'block' (float32)."""
+    """selector (3 -> C) -> 'src' (float32: the block reads nothing else) -> [dw 3x3 + ReLU -> 1x1 + ReLU] -> 'block' (float32).
+    Each output row draws 4 weights of +-1, +-2; the input channels left without one then get one (cover_inputs), a row without a
+    positive weight gets one, and the depthwise taps of an all-negative 'src' channel are negative: a channel that reaches no output,
+    through a zero weight or a ReLU that cuts it everywhere, cannot show a wrong tap, bias or slab (the CPU tests perturb them).  |src| <= 3 * 2 * 255 + 16 = 1546, |mid| <= 9 * 1546 + 50 < 2^14, and a row of
+    C = 1024 into 64 outputs has about 16 weights: 16 * 2 * 13964 + 20 < 2^19, far below the 2^24 of the float32-only 'block'."""
     rng = np.random.default_rng(seed * 100000 + C * 300 + cout + stride)
     net = Net(precision)
-    selector(net, rng, 'src', C, wmax=2)
+    net.tensor('src', C, 1)
+    Ws, bs = selector_weights(rng, C, 1, 2)        # (selector(): the same draw)
+    idle = np.flatnonzero(~Ws.any(axis=(1, 2, 3)))   # a channel of three zero weights is one constant: no tap of it could be told from another
+    Ws[idle, idle % 3, 0, 0] = np.where(idle % 8 == 5, -1.0, 1.0)
+    net.conv('input', 'src', Ws, bs)
     Wd, bd = dw_weights(rng, C, center=1)
-    Wp, bp = sparse_weights(rng, (cout, C, 1, 1), 4, values=(-2, -1, 1, 1, 2, 2))
+    values = (-2, -1, 1, 1, 2, 2)
+    Wp, bp = sparse_weights(rng, (cout, C, 1, 1), 4, values=values)
+    cover_inputs(rng, Wp, values)
+    # Signs, not magnitudes: half the channels of 'src' have one sign throughout (selector weights of one sign), and taps or a row that
+    # lean against the mean of what they read are 0 behind their ReLU at EVERY pixel.  Turn those round, by the means of uniform pixels.
+    sel = net.steps[-1][3]
+    src_mean = 127.5 * sel['W'].sum(axis=(1, 2, 3)) + sel['b']
+    Wd[Wd.sum(axis=(1, 2, 3)) * src_mean < 0] *= -1
+    mid_mean = np.maximum(Wd.sum(axis=(1, 2, 3)) * src_mean + bd, 0.0)
+    Wp[Wp[:, :, 0, 0] @ mid_mean + bp < 0] *= -1
     net.tensor('block', cout, 0, f32=True)
     net.dwpw('src', 'block', Wd, bd, Wp, bp, stride=stride)
     return net
@@ -955,9 +983,113 @@ COPY_CASES = {                                                       # (c_src, c
 }
 COPY_SHAPES = ((1, 1), (5, 7), (9, 16))
 CONVPOOL_SHAPES = ((2, 2), (5, 7), (8, 8), (9, 16))
-DWPW_CASES = ((64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (32, 32, 1), (32, 64, 2), (96, 40, 1), (64, 24, 1))
-DWPW_SHAPES = ((5, 7), (9, 16))
+DWPW_CASES = ((64, 64, 1), (64, 128, 2), (128, 128, 1), (128, 256, 2), (256, 256, 1), (32, 32, 1), (32, 64, 2), (96, 40, 1), (64, 24, 1),
+              # more than 256 input channels (dwpw_table_loader: the depthwise table's tail loop); the last: two cout tiles as well
+              (320, 64, 1), (1024, 64, 1), (1024, 128, 1), (320, 256, 1))
+# frames (h, w) of two images, or (n, h, w).  At stride 1 the block's map is the frame's: M = 70 and 288 (several images in a partial
+# tile); 64, 128, 256 (whole tiles of 64 and of 128 pixels); 63 | 65 and 127 | 129 (one pixel either side); 126 (2 x 7 x 9: tile 0 of
+# 64 holds image 0 and ONE pixel of image 1, both of an odd Ho Wo) and 130 (2 x 5 x 13: the 128-pixel tile likewise)
+DWPW_SHAPES = ((5, 7), (9, 16), (4, 8), (8, 8), (8, 16), (3, 3, 7), (1, 5, 13), (1, 1, 127), (1, 3, 43), (7, 9), (5, 13))
+DWPW_BIG_C_SHAPES = ((5, 7),)                    # what the cases of more than 256 input channels run: M = 70
+# (C, cout, stride) -> frames: more than 8 pixel tiles, so that ta_xcd_tile deals whole rounds (base >= 1) and a remainder -- what
+# every launch of the real detector does.  2 x 23 x 23: M = 1058 = 9 tiles of 128, 17 of 64; 2 x 45 x 48 at stride 2: an odd x even
+# map of 23 x 24, M = 1104 = 9 tiles of 128, 18 of 64
+DWPW_MANY_TILES = {(64, 64, 1): (2, 23, 23), (128, 128, 1): (2, 23, 23), (64, 24, 1): (2, 23, 23), (64, 128, 2): (2, 45, 48), (32, 64, 2): (2, 45, 48)}
 RFSTEM_SHAPES = ((1, 27, 123), (1, 29, 125), (2, 57, 249), (1, 5, 7), (1, 56, 248), (1, 31, 126), (3, 16, 16))
+# The fused front's own geometry (rfstem_fused_geometry: 6 x 30 tiles of the quarter-resolution map), what each shape is for:
+#   1 x 21 x 117  exactly one tile (oh, ow = 6, 30), 3 W mod 4 = 3, mh = 11 and mw = 59 odd: the tile's last row and column read
+#                 row 11 / column 59 of the 16-channel map, which lie outside it
+#   2 x 23 x 118  one tile, 3 W mod 4 = 2, mh = 12 even, mw = 59 odd; the second image starts 2 bytes off a dword
+#   2 x 23 x 119  one tile, 3 W mod 4 = 1, mh = 12, mw = 60 even; the second image starts 3 bytes off
+#   1 x 24 x 120  one tile, 3 W mod 4 = 0, mh = 12, mw = 60: the largest frame of one tile
+#   2 x 25 x 121  one output row and column more than a tile (7 x 31); second image 3 bytes off
+#   1 x 43 x 235  one row and column less than two tiles (11 x 59)
+#   1 x 48 x 240  exactly 2 x 2 tiles
+#   2 x 47 x 245  the smallest width at which a tile (column 1 of 3) copies its window unmasked (x_inside)
+#   3 x 49 x 244  one pixel narrower: no tile is x_inside; three tile rows (oh = 13)
+#   1 x 5 x 7     a frame smaller than one window
+RFSTEM_FUSED_SHAPES = ((1, 21, 117), (2, 23, 118), (2, 23, 119), (1, 24, 120), (2, 25, 121), (1, 43, 235), (1, 48, 240), (2, 47, 245),
+                       (3, 49, 244), (1, 5, 7))
+RFSTEM_ALL_SHAPES = RFSTEM_SHAPES + tuple(s for s in RFSTEM_FUSED_SHAPES if s not in RFSTEM_SHAPES)
+
+
+def dwpw_shapes(C, cout=None, stride=None):
+    """The (n, h, w) frames test_dwpw runs a case of DWPW_CASES on."""
+    return tuple(s if len(s) == 3 else (2,) + s for s in (DWPW_BIG_C_SHAPES if C > 256 else DWPW_SHAPES))
+
+
+# ---- the tiling of the two detector kernels, mirrored from the .hip files (tests/test_exact_programs_cpu.py proves from these that
+# ---- the lists above reach every path they are listed for) ------------------------------------------------------------------------
+RFS_OY, RFS_OX = 6, 30                           # csrc/layers.hip:236-237: output tile of rf_stem_kernel<true>
+RFS_IXB = (2 * (62 + 2) + 1) * 3                 # csrc/layers.hip:210-214: bytes per window row (387)
+
+
+def rfstem_fused_geometry(h, w):
+    """rf_stem_kernel<true> on h x w frames (csrc/layers.hip:551-552, 572: ta_launch_rfstem; 247-249, 262: the kernel).  -> dict:
+    mh, mw the 16-channel half-resolution map; oh, ow the quarter-resolution output; tiles_y, tiles_x the grid; origin(by, bx) the
+    frame (row, column) of a tile's window; x_inside(bx) whether the tile copies its window rows as unmasked dwords."""
+    mh, mw = (h + 1) // 2, (w + 1) // 2
+    oh, ow = (mh + 1) // 2, (mw + 1) // 2
+
+    def origin(by, bx):
+        ty0, tx0 = 2 * RFS_OY * by - 1, 2 * RFS_OX * bx - 1          # layers.hip:247-248 (FUSE)
+        return 2 * (ty0 - 1) - 1, 2 * (tx0 - 1) - 1                  # layers.hip:249: iy0, ix0 = 24 by - 5, 120 bx - 5
+
+    def x_inside(bx):
+        ix0 = origin(0, bx)[1]
+        return ix0 >= 0 and ix0 * 3 + RFS_IXB + 3 <= w * 3          # layers.hip:262
+
+    return dict(mh=mh, mw=mw, oh=oh, ow=ow, tiles_y=-(-oh // RFS_OY), tiles_x=-(-ow // RFS_OX), origin=origin, x_inside=x_inside)
+
+
+def dwpw_tile(cout, lean):
+    """(BN, BM) of the block's launch: csrc/conv_dwpw.hip:452-454 with :163 (rf_dwpw_kernel, `lean`), :456-462 with :21-22 (conv_dwpw)."""
+    coutp = -(-cout // 32) * 32
+    if coutp % 128 == 0:
+        return (128, 64) if lean else (128, 128)
+    if coutp % 64 == 0:
+        return (64, 64) if lean else (64, 128)
+    return 32, 128
+
+
+def xcd_tile(n_pt, xcd, local):
+    """csrc/conv_common.h:101-105: ta_xcd_tile."""
+    base, rem = n_pt >> 3, n_pt & 7
+    if local >= base + (1 if xcd < rem else 0):
+        return -1
+    return xcd * base + min(xcd, rem) + local
+
+
+def dwpw_grid(cout, M, lean):
+    """-> dict(BN, BM, n_ct, n_pt, blocks, tiles): csrc/conv_dwpw.hip:171-178 (:34-42) and conv_common.h:921 (ta_tile_grid);
+    tiles[b] = (ct, pt) of block b, pt < 0 for a block that returns at once."""
+    BN, BM = dwpw_tile(cout, lean)
+    n_ct, n_pt = -(-cout // 32) * 32 // BN, -(-M // BM)
+    blocks = -(-n_pt // 8) * n_ct * 8
+    tiles = [((b >> 3) % n_ct, xcd_tile(n_pt, b & 7, (b >> 3) // n_ct)) for b in range(blocks)]
+    return dict(BN=BN, BM=BM, n_ct=n_ct, n_pt=n_pt, blocks=blocks, tiles=tiles)
+
+
+def dwpw_lean_ok(precision, C, cout):
+    """csrc/conv_dwpw.hip:446-450: the f16x3 launch takes rf_dwpw_kernel (the programs here: ReLU, float32 out, n_slabs 32 == C)."""
+    return precision == 'f16x3' and C % 32 == 0 and C <= 1024 and cout % 8 == 0
+
+
+DWPW_TABLE_FIRST = 3 * 256                       # csrc/conv_dwpw.hip:193-200: granules the unrolled prologue loads (WG = 3 per thread)
+LDS_PER_CU = 160 * 1024                          # gfx950
+
+
+def dwpw_table_loader(C, row, c):
+    """Which loop of rf_dwpw_kernel puts value (row, c) of the depthwise table [9 taps + bias][C] into LDS (row 9: the bias):
+    -> (granule, trip); trip 0: the unrolled prologue (conv_dwpw.hip:196-200, 323-325), trip k >= 1: pass k of the tail loop (:326-327)."""
+    g = (row * C + c) // 4
+    return g, 0 if g < DWPW_TABLE_FIRST else 1 + (g - DWPW_TABLE_FIRST) // 256
+
+
+def dwpw_lean_lds(C, cout):
+    """csrc/conv_dwpw.hip:411: two stages and the table."""
+    BN, BM = dwpw_tile(cout, True)
+    return 2 * (BN + BM) * 32 * 4 + 40 * C
 
 # One case per grid-stride kernel whose work items (the `total` of its ta_launch_*) just exceed the 2048 x 256 threads a launch is
 # capped at, so that the loop's second trip runs: (frame h, w) and the total, for one image, float32.

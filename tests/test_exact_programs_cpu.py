@@ -230,16 +230,186 @@ def test_convpool_program(precision):
 @pytest.mark.parametrize('C,cout,stride', ep.DWPW_CASES)
 def test_dwpw_programs(precision, C, cout, stride):
     net = ep.dwpw_net(precision, C, cout, stride)
-    ref = check(net, ep.DWPW_SHAPES)
+    refs = {}
+    for shape in ep.dwpw_shapes(C) + ((ep.DWPW_MANY_TILES[(C, cout, stride)],) if (C, cout, stride) in ep.DWPW_MANY_TILES else ()):
+        refs[shape] = check(net, [shape], seed=700)                 # the frames test_dwpw runs
+        if precision == 'f16x3':                                    # the range guard watches the float32 store of 'block' as well
+            in_half_range(refs[shape]['block'], net.P.scales[net.tid['block']], 'block')
+    ref = refs[(2, 5, 7) if C > 256 else (2, 9, 16)]
     assert formats(net)['src'] == pack.FMT_F32
     assert ref['block'].max() > 2048 and (ref['block'] == 0).any() and (ref['block:mid'] == 0).any()      # both ReLUs cut something
+    assert (ref['block'] > 0).any(axis=(0, 2, 3)).all() and (ref['block:mid'] > 0).any(axis=(0, 2, 3)).all()      # ... but no channel whole
+    Wp = net.steps[-1][3]['Wp'][:, :, 0, 0]
+    assert Wp.any(axis=0).all() and np.array_equal(Wp, np.rint(Wp)) and np.abs(Wp).max() == 2      # every input channel reaches an output
+
+
+# ---- dw+pw: what the sizes and cases reach, proved from the mirror of the kernels' tiling (ep.dwpw_grid) ---------------------------
+def _dwpw_M(shape, stride):
+    n, h, w = shape
+    return n * ((h - 1) // stride + 1) * ((w - 1) // stride + 1)
+
+
+def test_dwpw_grid_mirror_deals_every_tile_once():
+    """ep.dwpw_grid (the mirror of ta_xcd_tile and the block -> (cout tile, pixel tile) arithmetic): every tile of every launch listed
+    has exactly one block, the other blocks of the grid return; an XCD's tiles are consecutive."""
+    for C, cout, stride in ep.DWPW_CASES:
+        shapes = ep.dwpw_shapes(C) + ((ep.DWPW_MANY_TILES[(C, cout, stride)],) if (C, cout, stride) in ep.DWPW_MANY_TILES else ())
+        for shape in shapes:
+            for lean in (True, False):
+                g = ep.dwpw_grid(cout, _dwpw_M(shape, stride), lean)
+                live = sorted(t for t in g['tiles'] if t[1] >= 0)
+                assert live == [(ct, pt) for ct in range(g['n_ct']) for pt in range(g['n_pt'])], (C, cout, stride, shape, lean)
+                assert g['BN'] * g['n_ct'] == -(-cout // 32) * 32 and g['blocks'] % 8 == 0
+                for xcd in range(8):
+                    mine = [pt for b, (ct, pt) in enumerate(g['tiles']) if b & 7 == xcd and ct == 0 and pt >= 0]
+                    assert mine == list(range(mine[0], mine[0] + len(mine))) if mine else g['n_pt'] < 8
+    assert [ep.dwpw_tile(c, True) for c in (24, 40, 64, 128, 256)] == [(32, 128), (64, 64), (64, 64), (128, 64), (128, 64)]
+    assert [ep.dwpw_tile(c, False) for c in (24, 40, 64, 128, 256)] == [(32, 128), (64, 128), (64, 128), (128, 128), (128, 128)]
+
+
+def test_dwpw_sizes_reach_the_tile_edges():
+    """Stride-1 cases of both pixel tiles of the lean kernel (BM 64 and 128) and of the generic kernel (BM 128) run DWPW_SHAPES, whose M
+    are whole tiles (exactly 1, 2 and 4 of 64; 1 and 2 of 128), one pixel either side of 64 and of 128, and a tile that holds the end
+    of one image and the start of the next, both of an odd Ho Wo."""
+    s1 = [(C, cout) for C, cout, stride in ep.DWPW_CASES if stride == 1 and C <= 256]
+    assert {ep.dwpw_tile(cout, True)[1] for _, cout in s1} == {64, 128} and {ep.dwpw_tile(cout, False)[1] for _, cout in s1} == {128}
+    assert {ep.dwpw_tile(cout, True)[0] for _, cout in s1} == {32, 64, 128}
+    shapes = ep.dwpw_shapes(64)
+    Ms = [_dwpw_M(s, 1) for s in shapes]
+    assert {63, 64, 65, 127, 128, 129, 256} <= set(Ms), Ms
+    for BM, whole in ((64, {1, 2, 4}), (128, {1, 2})):
+        assert whole <= {M // BM for M in Ms if M % BM == 0}, (BM, Ms)
+        # a tile with the last pixel of image 0 and the first of image 1, Ho Wo odd
+        assert any(n >= 2 and h * w % 2 == 1 and h * w % BM and (h * w - 1) // BM == h * w // BM for n, h, w in shapes), BM
+    assert (2, 7, 9) in shapes and (2, 5, 13) in shapes        # 63 + 1 in a tile of 64; 65 + 63 in a tile of 128
+
+
+def test_dwpw_many_tiles_cases_deal_rounds_and_a_remainder():
+    """More than 8 pixel tiles in the lean and in the generic kernel: ta_xcd_tile with base >= 1 and rem > 0, so that XCDs own
+    different numbers of tiles; n_pt = 9 at BM = 128 and 17 at BM = 64 (stride 1), and a stride-2 case on an odd x even map."""
+    seen, tiles = set(), set()
+    for (C, cout, stride), shape in ep.DWPW_MANY_TILES.items():
+        assert (C, cout, stride) in ep.DWPW_CASES
+        n, h, w = shape
+        M = _dwpw_M(shape, stride)
+        for lean in (True, False):
+            g = ep.dwpw_grid(cout, M, lean)
+            assert g['n_pt'] > 8 and g['n_pt'] >> 3 >= 1 and g['n_pt'] & 7, (C, cout, stride, lean, g['n_pt'])
+            assert any(pt < 0 for _, pt in g['tiles'])                # some blocks of the last round have no tile
+            seen.add((stride, g['BM'], g['n_pt'], lean))
+            tiles.add((stride, g['BN'], lean))
+        if stride == 2:
+            assert ((h - 1) // 2 + 1) % 2 == 1 and ((w - 1) // 2 + 1) % 2 == 0
+    assert {(1, 128, 9, True), (1, 64, 17, True), (1, 128, 9, False)} <= seen, seen
+    assert any(s == 2 and lean for s, _, _, lean in seen) and any(s == 2 and not lean for s, _, _, lean in seen)
+    assert {g for _, g, _, lean in seen if lean} == {64, 128}          # both pixel tiles of the lean kernel
+    assert {(1, 32, True), (1, 64, True), (1, 128, True), (2, 64, True), (2, 128, True)} <= tiles, tiles      # every instance of it, both strides
+
+
+BIG_C = [c for c in ep.DWPW_CASES if c[0] > 256]
+
+
+def test_dwpw_big_c_cases_reach_the_table_tail_loop():
+    """C = 320: 800 granules, the tail loop loads bias values only; C = 1024: 2560 granules, seven passes of it over tap rows 3 .. 8
+    and the bias.  Both take rf_dwpw_kernel (lean_ok), within the LDS of a CU; one case has two cout tiles."""
+    assert {c[0] for c in BIG_C} == {320, 1024} and max(c[0] for c in ep.DWPW_CASES if c not in BIG_C) == 256
+    for C, cout, stride in BIG_C:
+        assert ep.dwpw_lean_ok('f16x3', C, cout) and not ep.dwpw_lean_ok('f32', C, cout)
+        assert ep.dwpw_lean_lds(C, cout) <= ep.LDS_PER_CU
+        trips = {(row, ep.dwpw_table_loader(C, row, c)[1]) for row in range(10) for c in range(0, C, 4)}
+        assert 10 * C // 4 > ep.DWPW_TABLE_FIRST and any(t for _, t in trips)
+        if C == 320:
+            assert {row for row, t in trips if t} == {9} and {t for _, t in trips} == {0, 1}
+            assert ep.dwpw_table_loader(C, 9, 192) == (768, 1) and ep.dwpw_table_loader(C, 9, 188)[1] == 0
+        else:
+            assert {row for row, t in trips if t} == set(range(3, 10)) and {t for _, t in trips} == set(range(8))
+            assert ep.dwpw_table_loader(C, 3, 0) == (768, 1) and ep.dwpw_table_loader(C, 9, C - 1) == (2559, 7)
+    assert max(ep.dwpw_lean_lds(C, cout) for C, cout, _ in BIG_C) == 2 * (128 + 64) * 128 + 40 * 1024      # 88 KB: the (1024, 128) case
+    assert not ep.dwpw_lean_ok('f16x3', 1056, 64)
+    assert {(C, cout) for C, cout, _ in BIG_C} >= {(320, 64), (1024, 64), (1024, 128)}
+    assert 2 in {ep.dwpw_grid(cout, 70, True)['n_ct'] for _, cout, _ in BIG_C}
+    # the shipped network's blocks never get there
+    assert all(10 * C // 4 <= ep.DWPW_TABLE_FIRST for C, _, _ in ep.DWPW_CASES if C <= 256)
+
+
+def _dwpw_sample(C):
+    """(row of the depthwise table, channel): channel 0, the last, one in every 32-channel slab (the tap walks the nine), and the
+    values whose granules lie at, just before and beyond 768, at every pass of the tail loop, and the last granule."""
+    out = {(0, 0), (8, C - 1), (9, 0), (9, C - 1)}
+    out |= {((s * 5 + 1) % 9, s * 32 + (s * 11 + 3) % 32) for s in range(C // 32)}
+    out |= {(9, s * 32 + (s * 7 + 5) % 32) for s in range(C // 32)}
+    out |= {(row, row * 37 % C) for row in range(10)}
+    for g in [ep.DWPW_TABLE_FIRST - 1] + list(range(ep.DWPW_TABLE_FIRST, 10 * C // 4, 256)) + [10 * C // 4 - 1]:
+        if g < 10 * C // 4:
+            row, c = divmod(g * 4, C)
+            out |= {(row, c), (row, c + 3)}
+    return sorted(out)
+
+
+@pytest.mark.parametrize('C,cout,stride', BIG_C + [(256, 256, 1), (64, 24, 1)])
+def test_dwpw_every_sampled_channel_reaches_the_output(C, cout, stride):
+    """One depthwise tap, then one depthwise bias, changed by 1 for a channel: the reference output must change each time.  (A channel
+    whose 1x1 weights are all zero, or whose rows the ReLU cuts everywhere, would be no test of that channel's taps, bias or slab.)"""
+    net = ep.dwpw_net('f32', C, cout, stride)
+    a = net.steps[-1][3]
+    n, h, w = ep.dwpw_shapes(C)[0]
+    fr = ep.frames(700 + h * 31 + w, n, h, w)
+    ref = ep.reference(net, fr)['block']
+    sample = _dwpw_sample(C)
+    assert {c // 32 for _, c in sample} == set(range(C // 32)) and {r for r, _ in sample} == set(range(10))
+    if C > 256:
+        trips = {ep.dwpw_table_loader(C, row, c)[1] for row, c in sample}
+        assert trips == set(range(2 if C == 320 else 8)), trips
+    for row, c in sample:
+        key, at = ('bd', (c,)) if row == 9 else ('Wd', (c, 0, row // 3, row % 3))
+        keep = a[key][at]
+        for delta in ((1.0,) if row == 9 else (1.0, -1.0)):            # (a tap of a pixel that is 0 there: try the other sign as well)
+            a[key][at] = keep + delta
+            changed = not np.array_equal(ep.reference(net, fr)['block'], ref)
+            a[key][at] = keep
+            if changed:
+                break
+        assert changed, (C, 'bias' if row == 9 else 'tap %d' % row, c)
+    assert np.array_equal(ep.reference(net, fr)['block'], ref)
+
+
+# ---- the fused front: what RFSTEM_FUSED_SHAPES reach, proved from ep.rfstem_fused_geometry ------------------------------------------
+def test_rfstem_fused_shapes_reach_the_tile_edges():
+    shapes = ep.RFSTEM_FUSED_SHAPES
+    assert len(shapes) <= 10 and all(h <= 49 and w <= 245 for _, h, w in shapes)
+    assert set(ep.RFSTEM_SHAPES) <= set(ep.RFSTEM_ALL_SHAPES) and set(shapes) <= set(ep.RFSTEM_ALL_SHAPES)
+    assert len(set(ep.RFSTEM_ALL_SHAPES)) == len(ep.RFSTEM_ALL_SHAPES)
+    G = {s: ep.rfstem_fused_geometry(s[1], s[2]) for s in shapes}
+    assert ep.rfstem_fused_geometry(24, 120)['origin'](1, 1) == (24 - 5, 120 - 5) and ep.rfstem_fused_geometry(24, 120)['origin'](0, 0) == (-5, -5)
+    tiles = {s: (g['tiles_y'], g['tiles_x']) for s, g in G.items()}
+    whole = {s: g for s, g in G.items() if g['oh'] % ep.RFS_OY == 0 and g['ow'] % ep.RFS_OX == 0}
+    # exactly one tile and exactly 2 x 2
+    assert {tiles[s] for s in whole} == {(1, 1), (2, 2)}
+    # one row and one column more than whole tiles, and one less
+    assert any((g['oh'], g['ow']) == (7, 31) for g in G.values()) and any(g['oh'] % 6 == 5 and g['ow'] % 30 == 29 for g in G.values())
+    # every row misalignment at a width of exactly one tile, mw odd and even; mh odd and even at the tile's last output row: output
+    # row oh - 1 reads row 2 oh - 1 of the 16-channel map, which is outside the map (staged as zero) when mh is odd
+    one = {s: g for s, g in whole.items() if tiles[s] == (1, 1)}
+    assert {3 * w % 4 for _, _, w in one} == {0, 1, 2, 3}
+    assert {g['mw'] % 2 for g in one.values()} == {0, 1} and {g['mh'] % 2 for g in one.values()} == {0, 1}
+    assert {2 * g['oh'] - 1 < g['mh'] for g in one.values()} == {True, False} and {2 * g['ow'] - 1 < g['mw'] for g in one.values()} == {True, False}
+    # the second image of a batch starts off a dword, at two residues at least
+    assert len({h * w * 3 % 4 for n, h, w in shapes if n >= 2} - {0}) >= 2
+    # x_inside: at W = 244 no tile, at W = 245 tile column 1 of three alone
+    at = {w: [G[s]['x_inside'](bx) for bx in range(G[s]['tiles_x'])] for s in shapes for w in [s[2]] if w in (244, 245)}
+    assert at == {244: [False, False, False], 245: [False, True, False]}, at
+    assert all(not g['x_inside'](bx) for s, g in G.items() if s[2] < 244 for bx in range(g['tiles_x']))
+    # smaller than one window (33 rows x 129 pixels from (-5, -5)), and three tile rows
+    assert (1, 5, 7) in shapes and any(g['tiles_y'] == 3 for g in G.values())
+    # the unfused 14 x 62 tiling keeps its own shapes
+    assert ep.RFSTEM_ALL_SHAPES[:len(ep.RFSTEM_SHAPES)] == ep.RFSTEM_SHAPES
 
 
 @pytest.mark.parametrize('fused', [False, True])
 def test_rfstem_programs(fused):
     net = ep.rfstem_net('f32', fused)
     lib.check_program(net.P)
-    for n, h, w in ep.RFSTEM_SHAPES:
+    for n, h, w in ep.RFSTEM_ALL_SHAPES:
         fr = ep.frames(50 + h, n, h, w)
         ref, want = ep.reference(net, fr), torch_replay(net, fr)
         assert np.array_equal(ref['front'], want['front'])

@@ -115,31 +115,63 @@ def test_conv_with_fused_pool_equals_conv_then_pool(ctx, precision):
 
 
 # ---- depthwise + pointwise block ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('precision', ['f32', 'f16x3'])
-@pytest.mark.parametrize('C,cout,stride', ep.DWPW_CASES)
-def test_dwpw(ctx, monkeypatch, precision, C, cout, stride):
-    """The (C, cout, stride) of test_rf_dwpw_kernel_equals_the_generic_kernel on odd maps, both kernels (TA_DWPW_GENERIC): not only
-    equal to each other but equal to the exact reference."""
+def _dwpw(ctx, monkeypatch, precision, C, cout, stride, shapes):
+    """The block on every frame size of `shapes` with the lean and the generic kernel (TA_DWPW_GENERIC): both equal to the exact
+    reference, computed once per size; ctx.kernel_work() names the kernel that ran."""
+    refs = {}
     for generic in (False, True):
         if generic:
             monkeypatch.setenv('TA_DWPW_GENERIC', '1')
         else:
             monkeypatch.delenv('TA_DWPW_GENERIC', raising=False)
         net = ep.dwpw_net(precision, C, cout, stride)
-        for h, w in ep.DWPW_SHAPES:
+        for n, h, w in shapes:
             ctx.kernel_work(reset=True)
-            run(ctx, net, ep.frames(700 + h * 31 + w, 2, h, w), ['src', 'block'], 'dwpw %s generic=%d' % (precision, generic))
+            refs[n, h, w] = run(ctx, net, ep.frames(700 + h * 31 + w, n, h, w), ['src', 'block'], 'dwpw %s generic=%d' % (precision, generic), ref=refs.get((n, h, w)))
             kernels = sorted(k for k in ctx.kernel_work() if 'dwpw' in k)
             lean = precision == 'f16x3' and not generic
+            assert lean == (ep.dwpw_lean_ok(precision, C, cout) and not generic)
             assert kernels and all(k.startswith('rf_dwpw_kernel' if lean else 'conv_dwpw') for k in kernels), kernels
         net.model.free()
 
 
+@pytest.mark.parametrize('precision', ['f32', 'f16x3'])
+@pytest.mark.parametrize('C,cout,stride', ep.DWPW_CASES)
+def test_dwpw(ctx, monkeypatch, precision, C, cout, stride):
+    """The (C, cout, stride) of test_rf_dwpw_kernel_equals_the_generic_kernel, both kernels (TA_DWPW_GENERIC): not only equal to each
+    other but equal to the exact reference.  ep.DWPW_SHAPES: odd maps, whole pixel tiles of 64 and of 128 (M = 64, 128, 256), one pixel
+    either side of them, tiles that hold the end of one odd image and the start of the next.  The cases of 320 and 1024 input channels
+    (on one 5 x 7 map) are the only runs of the loop that loads the depthwise table beyond its first 768 granules, with 88 KB of LDS at
+    (1024, 128); in 'f16x3' they must run rf_dwpw_kernel itself.  tests/test_exact_programs_cpu.py proves all of this from the
+    mirror of the kernels' tiling, and that every sampled input channel reaches the output."""
+    _dwpw(ctx, monkeypatch, precision, C, cout, stride, ep.dwpw_shapes(C))
+
+
+@pytest.mark.parametrize('precision', ['f32', 'f16x3'])
+@pytest.mark.parametrize('C,cout,stride', sorted(ep.DWPW_MANY_TILES))
+def test_dwpw_many_tiles(ctx, monkeypatch, precision, C, cout, stride):
+    """More than 8 pixel tiles: ta_xcd_tile deals whole rounds and a remainder over the 8 XCDs, as in every launch of the real
+    detector (9 tiles of 128 pixels, 17 or 18 of 64; stride 2 on an odd x even map)."""
+    shape = ep.DWPW_MANY_TILES[C, cout, stride]
+    n, h, w = shape
+    M = n * ((h - 1) // stride + 1) * ((w - 1) // stride + 1)
+    for lean in (True, False):
+        g = ep.dwpw_grid(cout, M, lean)
+        assert g['n_pt'] > 8 and g['n_pt'] & 7, g['n_pt']
+    _dwpw(ctx, monkeypatch, precision, C, cout, stride, [shape])
+
+
 # ---- RetinaFace front -----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('shape', ep.RFSTEM_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', ep.RFSTEM_ALL_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 def test_rfstem(ctx, shape):
-    """rf_stem_kernel, unfused and fused with the next block, at the tile edges of test_retinaface_front_tile_edges, with sparse
-    +-1 integer weights."""
+    """rf_stem_kernel, unfused and fused with the next block, with sparse +-1 integer weights.  ep.RFSTEM_SHAPES are the edges of the
+    unfused kernel's 14 x 62 tiles of the half-resolution map.  ep.RFSTEM_FUSED_SHAPES are those of rf_stem_kernel<true>, which writes
+    6 x 30 tiles of the quarter-resolution map (a 24 x 120 step in frame pixels, window from frame row 24 by - 5, column 120 bx - 5):
+    21..24 x 117..120 exactly one tile at every row misalignment 3 W mod 4, with mh and mw odd (the tile's last row / column reads a
+    16-channel pixel outside the map: staged as zero) and even; 25 x 121 and 43 x 235 one more and one less than whole tiles;
+    48 x 240 exactly 2 x 2; 47 x 245 the smallest width at which a tile takes the unmasked x_inside copy and 49 x 244 the largest
+    at which none does (three tile rows); batches whose second image starts 2 and 3 bytes off a dword; 5 x 7 smaller than a window.
+    tests/test_exact_programs_cpu.py proves each from ep.rfstem_fused_geometry."""
     for fused in (False, True):
         net = ep.rfstem_net('f32', fused)
         run(ctx, net, ep.frames(50 + shape[1], *shape), ['front'], 'rfstem fused=%d' % fused)

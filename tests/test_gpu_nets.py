@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests import exact_programs as ep
 from tests.util import golden, lane_sharing_program, two_conv_program
 from terran_amd import pack, synth
 
@@ -165,11 +166,12 @@ def test_failed_plan_leaves_the_model_as_it_was(ctx):
     m.free()
 
 
-@pytest.mark.parametrize('shape', [(1, 27, 123), (1, 29, 125), (2, 57, 249), (1, 5, 7), (1, 56, 248), (1, 31, 126), (3, 16, 16)],
-                         ids=lambda s: 'x'.join(map(str, s)))
+@pytest.mark.parametrize('shape', ep.RFSTEM_ALL_SHAPES, ids=lambda s: 'x'.join(map(str, s)))
 def test_retinaface_front_tile_edges(ctx, states, shape):
-    """rf_stem_kernel works on 14 x 62 output tiles from aligned dwords of the frame rows: maps of exactly one tile / one
-    pixel more, every row misalignment (W * 3 mod 4 = 0..3), frames smaller than a tile; the stride-8 / 16 / 32 features
+    """The fused front (rf_stem_kernel<true>: 6 x 30 output tiles of the quarter-resolution map, from aligned dwords of the frame
+    rows) at the shapes of tests/exact_programs.py: RFSTEM_SHAPES (the edges of the unfused 14 x 62 tiling) and RFSTEM_FUSED_SHAPES
+    (maps of exactly one and 2 x 2 fused tiles, one more and one less, every row misalignment W * 3 mod 4 = 0..3 with odd and even
+    half-resolution sizes, both sides of the x_inside width 245, frames smaller than a window); the stride-8 / 16 / 32 features
     (everything downstream of the front) against the oracle."""
     from terran_amd import lib
     _prec[0] = 'f32'
