@@ -758,6 +758,36 @@ int ta_arcface_embed_faces_multi(ta_model* m, const ta_frames* const* frames, in
 /* Cosine distance matrix 1 - a.b/(|a||b|) (examples/match.py:38): a (na,dim), b (nb,dim) -> (na,nb). */
 int ta_cosine_distance(ta_ctx* ctx, const float* a, int na, const float* b, int nb, int dim, float* out);
 
+/* ---- gallery: who is this face? (examples/match.py:30-41 asked of a watch-list) --------- */
+/* A grow-only set of `dim`-float embeddings (dim 1..1024) resident on the device, stored L2-normalised, each with a
+ * caller-chosen int32 id >= 0 (several rows may share an id).  Rows keep their index for the gallery's life: removing
+ * marks a row, it does not move the others.  At most 2^31-1 rows (TA_E_INVALID beyond).  `reserve_rows` allocates ahead;
+ * growth doubles the buffer with a device copy.  A gallery grown in steps answers bit for bit like one reserved up front. */
+typedef struct ta_gallery ta_gallery;
+int ta_gallery_create(ta_ctx* ctx, int dim, int64_t reserve_rows, ta_gallery** out);
+void ta_gallery_free(ta_gallery* g);
+/* Appends n rows (n, dim) with their ids (>= 0).  normalize != 0: each row is divided by its float32 L2 norm as
+ * ta_arcface_embed_* does (a zero row stays zero); 0: the rows are stored as given (they should have unit length). */
+int ta_gallery_add(ta_gallery* g, const float* rows, const int32_t* ids, int64_t n, int normalize);
+/* Every live row that carries one of the n ids is marked removed (its stored id becomes -1) and never found again;
+ * *removed = how many rows that were. */
+int ta_gallery_remove(ta_gallery* g, const int32_t* ids, int n, int64_t* removed);
+/* Forgets every row (the memory is kept); row indices start at 0 again. */
+int ta_gallery_clear(ta_gallery* g);
+/* *rows = rows ever added since the last clear (removed ones included: the range of row indices), *live = those not removed. */
+int ta_gallery_size(const ta_gallery* g, int64_t* rows, int64_t* live);
+/* The stored (normalised) rows (rows, dim) and ids (rows,), -1 for removed rows: ta_gallery_add(..., normalize = 0) of them
+ * into a fresh gallery rebuilds this one bit for bit. */
+int ta_gallery_download(const ta_gallery* g, float* rows_out, int32_t* ids_out);
+/* The k (1..16) nearest live rows of each of nq queries (nq, dim) by cosine distance 1.0f - dot(query, row) in float32
+ * (normalize != 0: the queries are L2-normalised first), ordered by (distance, row index) ascending: ties go to the
+ * lower row.  out_row / out_id / out_dist are (nq, k); with fewer than k live rows the tail is (-1, -1, +inf).
+ * nq == 0 and an empty gallery succeed.  The result does not depend on how the gallery was grown.
+ * Rows and queries must be finite; they are not checked.  A NaN or infinite component gives NaN distances, which take the
+ * place their bit pattern gives them (sign bit clear: behind +inf; set: in front of every number) and mean nothing. */
+int ta_gallery_search(ta_gallery* g, const float* queries, int nq, int k, int normalize, int32_t* out_row, int32_t* out_id,
+                      float* out_dist);
+
 /* ---- OpenPose.call (openpose/wrapper.py:182-485) ---------------------------------------- */
 /* frames: uint8 RGB ALREADY at network resolution (the wrapper's resize is ta_frames_resize);
  * scale = short_side / min(H_orig, W_orig) maps keypoints back ((coord/scale) truncated).

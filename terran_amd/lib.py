@@ -104,6 +104,14 @@ SIGNATURES = {
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                              c_void_p]),
     'ta_cosine_distance': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
+    'ta_gallery_create': (c_int, [c_void_p, c_int, C.c_int64, P(c_void_p)]),
+    'ta_gallery_free': (None, [c_void_p]),
+    'ta_gallery_add': (c_int, [c_void_p, c_void_p, c_void_p, C.c_int64, c_int]),
+    'ta_gallery_remove': (c_int, [c_void_p, c_void_p, c_int, P(C.c_int64)]),
+    'ta_gallery_clear': (c_int, [c_void_p]),
+    'ta_gallery_size': (c_int, [c_void_p, P(C.c_int64), P(C.c_int64)]),
+    'ta_gallery_download': (c_int, [c_void_p, c_void_p, c_void_p]),
+    'ta_gallery_search': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     'ta_openpose_run': (c_int, [c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_openpose_group': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p,
                                   c_void_p, c_void_p, P(C.c_int32)]),
@@ -117,6 +125,9 @@ SIGNATURES = {
     'ta_debug_conv_counts': (c_int, [c_void_p, c_void_p, c_int]),
     'ta_debug_kernel_work': (c_int, [c_void_p, C.c_char_p, c_size_t, c_int]),
 }
+
+# gallery.hip: rows per workgroup tile, queries per MFMA group, the largest k of ta_gallery_search
+GALLERY_ROW_TILE, GALLERY_QUERY_GROUP, GALLERY_MAX_K = 128, 32, 16
 
 # ta_draw_prim (include/terran_amd.h) and its kinds TA_DRAW_*
 DRAW_BAR, DRAW_LINE, DRAW_DISC, DRAW_MASK = 0, 1, 2, 3
@@ -937,6 +948,73 @@ class Frames:
     def free(self):
         if getattr(self, 'h', None) and getattr(self.ctx, 'h', None):
             self.ctx.lib.ta_frames_free(self.h)
+        self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Gallery:
+    """ta_gallery: `dim`-float embeddings resident in HBM, each with an int32 id >= 0, searched by cosine distance."""
+
+    def __init__(self, ctx, dim, reserve=0):
+        self.ctx = ctx
+        self.dim = int(dim)
+        h = c_void_p()
+        ctx.check(ctx.lib.ta_gallery_create(ctx.h, self.dim, int(reserve), C.byref(h)))
+        self.h = h
+
+    def _rows(self, a, what):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != self.dim:
+            raise TerranAmdError(E_INVALID, 'gallery: %s of shape %s are not (n, %d)' % (what, a.shape, self.dim))
+        return a
+
+    def add(self, rows, ids, normalize=True):
+        rows = self._rows(rows, 'rows')
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        if len(ids) != len(rows):
+            raise TerranAmdError(E_INVALID, 'gallery: %d ids for %d rows' % (len(ids), len(rows)))
+        self.ctx.check(self.ctx.lib.ta_gallery_add(self.h, ptr(rows), ptr(ids), len(rows), int(bool(normalize))))
+
+    def remove(self, ids):
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        removed = C.c_int64()
+        self.ctx.check(self.ctx.lib.ta_gallery_remove(self.h, ptr(ids) if len(ids) else None, len(ids), C.byref(removed)))
+        return removed.value
+
+    def clear(self):
+        self.ctx.check(self.ctx.lib.ta_gallery_clear(self.h))
+
+    def size(self):
+        """(rows, live rows)."""
+        rows, live = C.c_int64(), C.c_int64()
+        self.ctx.check(self.ctx.lib.ta_gallery_size(self.h, C.byref(rows), C.byref(live)))
+        return rows.value, live.value
+
+    def download(self):
+        """(stored rows (n, dim) float32, ids (n,) int32 with -1 for removed rows)."""
+        n = self.size()[0]
+        rows, ids = np.empty((n, self.dim), np.float32), np.empty(n, np.int32)
+        self.ctx.check(self.ctx.lib.ta_gallery_download(self.h, ptr(rows), ptr(ids)))
+        return rows, ids
+
+    def search(self, queries, k=1, normalize=True):
+        """(row, id, distance) arrays of shape (nq, k); padded slots are (-1, -1, +inf)."""
+        q = self._rows(queries, 'queries')
+        k = int(k)
+        kk = max(k, 0)
+        row, ident = np.empty((len(q), kk), np.int32), np.empty((len(q), kk), np.int32)
+        dist = np.empty((len(q), kk), np.float32)
+        self.ctx.check(self.ctx.lib.ta_gallery_search(self.h, ptr(q), len(q), k, int(bool(normalize)), ptr(row), ptr(ident), ptr(dist)))
+        return row, ident, dist
+
+    def free(self):
+        if getattr(self, 'h', None) and getattr(self.ctx, 'h', None):
+            self.ctx.lib.ta_gallery_free(self.h)
         self.h = None
 
     def __del__(self):

@@ -1,0 +1,118 @@
+"""Tools: time FaceGallery's search (lib.Gallery.search) on a resident gallery of 512-float embeddings.  Per case -- q queries,
+k results, n rows -- the device time of the two search kernels (HIP events: the library's profiling class of the
+post-processing kernels), the device time of the whole call (events around it: query upload, kernels, results back) and
+its wall time.  Yardsticks of the same run: one read of the gallery's bytes at the rate `point_frames` reaches on a
+32 x 1080p batch (frames read and written), `ctx.cosine_distance` + a host argpartition for 64 queries over 10^5 rows (the only
+way to the same answer without the gallery), and numpy on 16 threads (float32 matrix product + argpartition).  One JSON line.
+
+    python tools/gallery_bench.py [--rows 100000 1000000] [--reps 10]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+os.environ.setdefault('OMP_NUM_THREADS', '16')
+
+import numpy as np      # noqa: E402
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from terran_amd import image, lib, runtime      # noqa: E402
+
+
+def med(x):
+    return round(float(np.median(x)), 4)
+
+
+def stream_rate(ctx, reps):
+    """GB/s of point_frames on 32 x 1080 x 1920 (bytes read + written over device time)."""
+    frames = lib.Frames.zeros(ctx, 32, 1080, 1920)
+    ident = np.zeros(32, lib.POINT_DT)
+    ident['frame'], ident['x1'], ident['y1'] = np.arange(32), 1920, 1080
+    table = np.tile(image.brightness_lut(1.1), 3)[None]
+    ms = []
+    for rep in range(3 + reps):
+        ctx.timer_start()
+        frames.point(ident, table)
+        d = ctx.timer_stop()
+        if rep >= 3:
+            ms.append(d)
+    frames.free()
+    return 2 * 32 * 1080 * 1920 * 3 / (min(ms) * 1e-3) / 1e9
+
+
+def time_search(ctx, g, q, k, reps, warmup=2):
+    kern, dev, wall = [], [], []
+    for rep in range(warmup + reps):
+        ctx.profile(True)
+        ctx.profile_reset()
+        g.search(q, k)
+        ctx.profile(False)
+        kms = ctx.profile_read(3)[0]
+        ctx.timer_start()
+        g.search(q, k)
+        d = ctx.timer_stop()
+        t0 = time.perf_counter()
+        g.search(q, k)
+        t1 = time.perf_counter()
+        if rep >= warmup:
+            kern.append(kms)
+            dev.append(d)
+            wall.append((t1 - t0) * 1e3)
+    return {'kernel_ms': med(kern), 'kernel_ms_min': round(min(kern), 4), 'device_ms': med(dev), 'wall_ms': med(wall)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--rows', type=int, nargs='+', default=[100000, 1000000])
+    ap.add_argument('--queries', type=int, nargs='+', default=[1, 32, 64, 256])
+    ap.add_argument('--k', type=int, nargs='+', default=[1, 8])
+    ap.add_argument('--dim', type=int, default=512)
+    ap.add_argument('--reps', type=int, default=10)
+    a = ap.parse_args()
+    ctx = runtime.get_context(0)
+    rng = np.random.default_rng(1)
+    out = {'metric': 'gallery search', 'dim': a.dim, 'reps': a.reps}
+    rate = stream_rate(ctx, a.reps)
+    out['stream_GBps'] = round(rate, 1)
+    for n in a.rows:
+        rows = rng.standard_normal((n, a.dim), dtype=np.float32)
+        g = lib.Gallery(ctx, a.dim, reserve=n)
+        t0 = time.perf_counter()
+        g.add(rows, np.arange(n, dtype=np.int32))
+        add_ms = (time.perf_counter() - t0) * 1e3
+        one_read_ms = n * a.dim * 4 / (rate * 1e9) * 1e3
+        block = {'add_wall_ms': round(add_ms, 1), 'one_read_ms': round(one_read_ms, 4), 'cases': {}}
+        for nq in a.queries:
+            q = rng.standard_normal((nq, a.dim), dtype=np.float32)
+            for k in a.k:
+                r = time_search(ctx, g, q, k, a.reps)
+                r['over_one_read'] = round(r['kernel_ms'] / one_read_ms, 2)
+                r['gallery_GBps'] = round(n * a.dim * 4 / (r['kernel_ms'] * 1e-3) / 1e9, 1)
+                block['cases']['q%d_k%d' % (nq, k)] = r
+        if n <= 100000:                                   # the ways to the same answer without the gallery, 64 queries, k = 8
+            q = rng.standard_normal((64, a.dim), dtype=np.float32)
+            wall = []
+            for rep in range(3):
+                t0 = time.perf_counter()
+                d = ctx.cosine_distance(q, rows)
+                idx = np.argpartition(d, 8, axis=1)[:, :8]
+                wall.append((time.perf_counter() - t0) * 1e3)
+            block['cosine_distance_argpartition_q64_k8_wall_ms'] = med(wall[1:])
+            rn = rows / np.linalg.norm(rows, axis=1, keepdims=True)
+            wall = []
+            for rep in range(3):
+                t0 = time.perf_counter()
+                d = 1.0 - (q / np.linalg.norm(q, axis=1, keepdims=True)) @ rn.T
+                idx = np.argpartition(d, 8, axis=1)[:, :8]      # noqa: F841
+                wall.append((time.perf_counter() - t0) * 1e3)
+            block['numpy_16_threads_q64_k8_wall_ms'] = med(wall[1:])
+        out['rows_%d' % n] = block
+        g.free()
+        del rows
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
