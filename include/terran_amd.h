@@ -787,6 +787,21 @@ int ta_gallery_download(const ta_gallery* g, float* rows_out, int32_t* ids_out);
  * place their bit pattern gives them (sign bit clear: behind +inf; set: in front of every number) and mean nothing. */
 int ta_gallery_search(ta_gallery* g, const float* queries, int nq, int k, int normalize, int32_t* out_row, int32_t* out_id,
                       float* out_dist);
+/* Which rows are the same person?  DBSCAN over the stored rows, indices 0 .. rows-1 (removed ones included in the index
+ * space).  i ~ j iff both rows are live and 1.0f - dot(row_i, row_j) < threshold in float32, the distance of
+ * ta_gallery_search; every unordered pair is decided once, so ~ is symmetric; a row is its own neighbour like any other
+ * (a zero row or one with a NaN component is nobody's).  degree_out[i] = number of j with i ~ j (0 for removed rows); a row
+ * is core iff its degree >= min_samples (>= 1).  Clusters are the connected components of ~ among core rows, numbered
+ * 0, 1, ... by ascending smallest core row; a live non-core row with a core neighbour joins the lowest-numbered cluster
+ * among its core neighbours'; every other row gets -1.  That is sklearn.cluster.DBSCAN(metric='precomputed') on the same
+ * adjacency, numbering included; min_samples = 1 is single linkage at the threshold.  labels_out / degree_out are (rows,);
+ * degree_out, n_clusters and rounds (the label propagation rounds the call ran) may be NULL.  The labels do not depend
+ * on how the gallery was grown or on anything the device schedules.  An empty gallery succeeds with *n_clusters = 0.
+ * TA_E_INVALID: min_samples < 1, a threshold that is not finite, labels_out NULL with rows > 0, more than 2^18 rows (the
+ * call allocates rows^2 / 8 bytes for its bit matrix, 8 GiB at the limit, and frees them before it returns).  TA_E_DEVICE:
+ * that allocation failed; the gallery is untouched. */
+int ta_gallery_cluster(ta_gallery* g, float threshold, int min_samples, int32_t* labels_out, int32_t* degree_out,
+                       int32_t* n_clusters, int32_t* rounds);
 
 /* ---- OpenPose.call (openpose/wrapper.py:182-485) ---------------------------------------- */
 /* frames: uint8 RGB ALREADY at network resolution (the wrapper's resize is ta_frames_resize);

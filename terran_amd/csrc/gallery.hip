@@ -14,26 +14,14 @@
 
 #include <algorithm>
 
-#include "ta_internal.h"
+#include "gallery.h"
 
-#define GAL_T 128    // rows per tile: 4 waves x 32 (lib.py: GALLERY_ROW_TILE)
 #define GAL_G 32     // queries per MFMA group (lib.py: GALLERY_QUERY_GROUP)
 #define GAL_KMAX 16  // largest k
 #define GAL_C 16     // candidate slots per query and selection round
 #define GAL_LDQ_PAD 4
 
-typedef float gal_f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long gal_u64;
 #define GAL_EMPTY 0xFFFFFFFFFFFFFFFFull
-
-struct ta_gallery {
-  ta_ctx* ctx;
-  int dim, ld;            // ld: floats per stored row (dim rounded up to 64)
-  int64_t cap, size, live;  // rows allocated (a multiple of GAL_T) / used (tombstones included) / used and not removed
-  float* rows;
-  int32_t* ids;
-  int n_cu;
-};
 
 // float32 -> uint32 with the same order (and back)
 __device__ __forceinline__ unsigned gal_ord(float d) {
@@ -89,11 +77,6 @@ __global__ __launch_bounds__(256) void gallery_remove_kernel(int32_t* ids, long 
       atomicAdd(removed, 1);
     }
   }
-}
-
-__device__ __forceinline__ void gal_load8(float4 (&a)[8], const float4* p) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) a[j] = p[2 * j];
 }
 
 // Pass 1.  NG = query groups of 32 a pass holds in LDS (2 while a row is at most 512 floats, else 1).

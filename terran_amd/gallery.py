@@ -11,6 +11,11 @@
 `scipy.spatial.distance.cosine` and keeps those under 0.5; here the known faces stay on the device (lib.Gallery:
 ta_gallery_* in include/terran_amd.h) and one call finds the k nearest of every query.  Names live on the host: every name
 owns one int32 id, and the rows added under it carry that id.
+
+Without a watch-list -- who appears in this video, and which faces are the same person? -- `cluster_faces` groups the
+faces of any number of frames by their embeddings (DBSCAN on the device, ta_gallery_cluster) and
+`cluster_representatives` picks the face to show for each group; `FaceGallery.cluster` does the same over an enrolled
+gallery, where two names in one cluster are probably one person.
 """
 import numpy as np
 
@@ -112,6 +117,22 @@ class FaceGallery:
                 face['distance'] = float(d)
         return faces
 
+    def cluster(self, threshold=0.5, min_samples=1):
+        """(labels, degree) over the stored rows, removed ones included: DBSCAN with cosine distance < threshold as the
+        neighbourhood (lib.Gallery.cluster).  labels[i] is row i's cluster, numbered by ascending smallest core row, or
+        -1 (noise, removed); degree[i] the number of rows within the threshold, the row itself included.
+        min_samples=1 is single linkage.  Two names in one cluster are probably one person, enrolled twice:
+
+            labels, _ = gallery.cluster()
+            _, ids = gallery._g.download()
+            for c in range(labels.max() + 1):
+                names = {gallery._names[i] for i in ids[labels == c] if i >= 0}
+                if len(names) > 1:
+                    print('one person?', sorted(names))
+        """
+        labels, degree, _, _ = self._g.cluster(threshold, min_samples)
+        return labels, degree
+
     # ---- persistence ----------------------------------------------------------------------
     def save(self, path):
         """One .npz: the stored (normalised) rows, their ids (-1: removed) and the names."""
@@ -139,3 +160,63 @@ class FaceGallery:
 
     def free(self):
         self._g.free()
+
+
+def cluster_representatives(labels, degree):
+    """One row per cluster, (n_clusters,) int64: the member with the most neighbours, ties to the lower row -- the chip to
+    show for "person 3".  Host only."""
+    labels, degree = np.asarray(labels).reshape(-1), np.asarray(degree).reshape(-1)
+    if len(labels) != len(degree):
+        raise ValueError('%d labels for %d degrees' % (len(labels), len(degree)))
+    n = int(labels.max()) + 1 if len(labels) else 0
+    reps = np.full(max(n, 0), -1, np.int64)
+    best = np.full(max(n, 0), -1, np.int64)
+    for row in np.nonzero(labels >= 0)[0]:
+        c = labels[row]
+        if degree[row] > best[c]:
+            best[c], reps[c] = degree[row], row
+    return reps
+
+
+def _rows_2d(f):
+    f = np.asarray(f, dtype=np.float32)
+    return f[None] if f.ndim == 1 else f
+
+
+def cluster_faces(faces, features, threshold=0.5, min_samples=1, text=None, ctx=None, device=None):
+    """Which faces are the same person?  faces: one image's list of face dicts, or a list of such lists (one per image);
+    features: what `extract_features` returned for them -- as `FaceGallery.identify` takes them.  The embeddings go into a
+    temporary gallery on the device and ONE cluster call groups them (DBSCAN, cosine distance < threshold, see
+    `FaceGallery.cluster`).  Every clustered face gets face['cluster'] = int; noise faces are left as they are.  With
+    text='person %d' a clustered face that has no face['text'] yet gets one, which `draw_faces(..., labels=True)`
+    writes; names from `identify` stay.  Returns (labels, representatives): labels (n_faces,) int32 in flat order,
+    representatives (n_clusters,) flat indices of the face to show per cluster (`cluster_representatives`)."""
+    nested = any(isinstance(f, (list, tuple)) for f in faces)
+    if nested:
+        if len(features) != len(faces):
+            raise ValueError('%d feature arrays for %d images' % (len(features), len(faces)))
+        flat = [face for per_image in faces for face in per_image]
+        parts = [_rows_2d(f) for per_image, f in zip(faces, features) if len(per_image)]
+        feats = np.concatenate(parts) if parts else np.empty((0, 0), np.float32)
+    else:
+        flat = list(faces)
+        feats = _rows_2d(features) if len(flat) else np.empty((0, 0), np.float32)
+    if feats.ndim != 2 or len(feats) != len(flat):
+        raise ValueError('%d embeddings for %d faces' % (len(feats) if feats.ndim else 0, len(flat)))
+    if not flat:
+        return np.empty(0, np.int32), np.empty(0, np.int64)
+    if ctx is None:
+        from . import runtime
+        ctx = runtime.get_context(device)
+    g = lib.Gallery(ctx, feats.shape[1], len(feats))
+    try:
+        g.add(np.ascontiguousarray(feats), np.zeros(len(feats), np.int32), True)
+        labels, degree, _, _ = g.cluster(threshold, min_samples)
+    finally:
+        g.free()
+    for face, label in zip(flat, labels):
+        if label >= 0:
+            face['cluster'] = int(label)
+            if text is not None and 'text' not in face:
+                face['text'] = text % int(label)
+    return labels, cluster_representatives(labels, degree)

@@ -112,6 +112,7 @@ SIGNATURES = {
     'ta_gallery_size': (c_int, [c_void_p, P(C.c_int64), P(C.c_int64)]),
     'ta_gallery_download': (c_int, [c_void_p, c_void_p, c_void_p]),
     'ta_gallery_search': (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    'ta_gallery_cluster': (c_int, [c_void_p, C.c_float, c_int, c_void_p, c_void_p, P(C.c_int32), P(C.c_int32)]),
     'ta_openpose_run': (c_int, [c_void_p, c_void_p, c_double, c_int, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_openpose_group': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_int, c_void_p,
                                   c_void_p, c_void_p, P(C.c_int32)]),
@@ -128,6 +129,8 @@ SIGNATURES = {
 
 # gallery.hip: rows per workgroup tile, queries per MFMA group, the largest k of ta_gallery_search
 GALLERY_ROW_TILE, GALLERY_QUERY_GROUP, GALLERY_MAX_K = 128, 32, 16
+# gallery_cluster.hip: ta_gallery_cluster pairs tiles of GALLERY_ROW_TILE rows; the most rows it takes (a bit matrix of 8 GiB)
+GALLERY_CLUSTER_MAX_ROWS = 1 << 18
 
 # ta_draw_prim (include/terran_amd.h) and its kinds TA_DRAW_*
 DRAW_BAR, DRAW_LINE, DRAW_DISC, DRAW_MASK = 0, 1, 2, 3
@@ -1011,6 +1014,15 @@ class Gallery:
         dist = np.empty((len(q), kk), np.float32)
         self.ctx.check(self.ctx.lib.ta_gallery_search(self.h, ptr(q), len(q), k, int(bool(normalize)), ptr(row), ptr(ident), ptr(dist)))
         return row, ident, dist
+
+    def cluster(self, threshold, min_samples=1):
+        """ta_gallery_cluster: (labels (rows,) int32 with -1 for noise and removed rows, degree (rows,) int32, number of
+        clusters, label propagation rounds run)."""
+        n = self.size()[0]
+        labels, degree = np.empty(n, np.int32), np.empty(n, np.int32)
+        count, rounds = C.c_int32(), C.c_int32()
+        self.ctx.check(self.ctx.lib.ta_gallery_cluster(self.h, float(threshold), int(min_samples), ptr(labels), ptr(degree), C.byref(count), C.byref(rounds)))
+        return labels, degree, count.value, rounds.value
 
     def free(self):
         if getattr(self, 'h', None) and getattr(self.ctx, 'h', None):
