@@ -600,6 +600,16 @@ typedef struct ta_combine_region {
 int ta_frames_combine(ta_ctx* ctx, ta_frames* dst, const ta_frames* src, const ta_frames* mask_frames,
                       const ta_combine_region* regions, int n, const uint8_t* masks, size_t mask_bytes);
 
+/* ---- tiles: cut many tiles of many frames in one launch (the front of tiled detection) ---------------------------------- */
+/* *out = a NEW resident batch (n, th, tw, 3): tile i is src[frame, y : y + th, x : x + tw], byte for byte.  One launch for
+ * all tiles; wide loads and stores whatever the byte alignment of the two sides; 64-bit offsets throughout.
+ * TA_E_INVALID: a tile that leaves its frame or a frame out of range (the message names the tile), th or tw <= 0.
+ * n == 0: TA_OK and *out = NULL. */
+typedef struct ta_tile {
+  int32_t frame, y, x;
+} ta_tile;
+int ta_frames_tiles(ta_ctx* ctx, const ta_frames* src, const ta_tile* tiles, int n, int th, int tw, ta_frames** out);
+
 /* ---- JPEG decode (terran/io/image.py: open_image = Pillow's Image.open(f).convert('RGB')) ------------------------------ */
 /* Baseline and extended-sequential Huffman JPEGs, 8-bit, 1 or 3 components in one interleaved scan, every component's
  * sampling ratio 1 or 2 in each direction (4:4:4, 4:2:2, 4:2:0, 4:4:0, grayscale), any width and height, restart
@@ -737,6 +747,36 @@ int ta_retinaface_run(ta_model* m, const ta_frames* frames, float score_thr, flo
 int ta_retinaface_postprocess(ta_ctx* ctx, const float* const heads[9], int n, int h, int w,
                               float score_thr, float nms_thr, int capacity, int32_t* counts,
                               float* boxes, float* landmarks, float* scores, int32_t* required);
+
+/* ---- tiled detection: detections of tiles -> detections of their frames ----------------------------------------------- */
+/* Candidates (host arrays: boxes (C,4), landmarks (C,5,2), scores (C,), float32, finite) come in GROUPS: the detections
+ * of one tile, or of one whole-frame pass, of one output frame.  Groups are sorted by frame and share no row; a row in
+ * no group is ignored.  Per candidate, in float32:
+ *   map    every coordinate v of its box and landmarks becomes v / zoom + o (one correctly rounded division, one
+ *          addition; o = ox for x, oy for y); scores are unchanged
+ *   edge   (edge > 0) it is dropped if its mapped box comes within `edge` pixels of an INTERIOR side of its group's
+ *          rectangle: bx1 < x0 + edge (left, bit 0), by1 < y0 + edge (top, bit 1), bx2 > x1 - edge (right, bit 2),
+ *          by2 > y1 - edge (bottom, bit 3): a face cut by the tile, which the overlapping neighbour sees whole
+ * Per frame the survivors are ordered by descending score (-0 = +0), equal scores by ascending row, and go through
+ * greedy NMS: ovr = inter / (area_a + area_b - inter) with area = (x2 - x1) * (y2 - y1), ta_retinaface_run's expression
+ * and operation order (metric 0), or inter / fminf(area_a, area_b), intersection over the smaller box (metric 1);
+ * suppressed iff ovr > nms_thr.  Outputs: the kept candidates per frame in that order, frames concatenated, counts[f]
+ * of frame f; out_source = each one's candidate row.  Capacity protocol of ta_retinaface_run: a short `capacity` gives
+ * TA_E_CAPACITY with *required and counts set.  Everything but the checks runs on the device; the suppression bit matrix
+ * lives in the context's scratch block (frames are processed in batches whose matrices fit 256 MiB).
+ * TA_E_OVERFLOW: more than 16384 candidates in the groups of one frame.  TA_E_INVALID: unsorted or overlapping groups, rows
+ * outside the arrays, zoom <= 0, an unknown metric, edge < 0. */
+typedef struct ta_merge_group {
+  int32_t frame;          /* which output frame this group of candidates belongs to; groups come sorted by frame    */
+  int32_t first, count;   /* its candidates: rows first .. first+count-1 of the candidate arrays                    */
+  float ox, oy, zoom;     /* frame = tile / zoom + origin                                                           */
+  float x0, y0, x1, y1;   /* the group's rectangle in frame coordinates                                             */
+  int32_t interior;       /* bit 0 left, 1 top, 2 right, 3 bottom: that side of the rectangle lies inside the frame */
+} ta_merge_group;
+int ta_detections_merge(ta_ctx* ctx, const ta_merge_group* groups, int n_groups, int n_frames, const float* boxes,
+                        const float* landmarks, const float* scores, int n_candidates, float nms_thr, int metric,
+                        float edge, int capacity, int32_t* counts, float* out_boxes, float* out_landmarks,
+                        float* out_scores, int32_t* out_source, int32_t* required);
 
 /* ---- ArcFace.call (arcface/wrapper.py:109-184) ------------------------------------------ */
 /* Embed n pre-cropped faces, uint8 (n,3,112,112) BGR.  normalize != 0 applies the row-wise L2

@@ -6,6 +6,7 @@ mirror `terran.face_detection / extract_features / pose_estimation`
 (terran/__init__.py:4-5): lazily-constructed `Detection`, `Recognition`, `Estimation`.
 """
 from .facade import Detection, Recognition, Estimation          # noqa: F401
+from .facade import TiledDetection                               # noqa: F401
 from .retinaface import RetinaFace                                # noqa: F401
 from .arcface import ArcFace                                      # noqa: F401
 from .openpose import OpenPose, PoseOverflow                      # noqa: F401

@@ -235,6 +235,82 @@ class Detection:
         return out[0] if expanded else out
 
 
+class TiledDetection:
+    """Face detection for frames whose faces are too small for `Detection`'s shrink to 416 pixels: every frame is cut into
+    overlapping `tile`-pixel tiles at its own resolution (times `zoom`), the detector runs on each (`full_frame`: and on
+    the whole frame at `short_side`, for the faces larger than a tile), and the detections are mapped back and suppressed
+    across tiles on the device (`RetinaFace.detect_tiles`; `tiles.py` has the tiling, include/terran_amd.h `edge` and
+    `metric`).  Accepts what `Detection` accepts on one device and returns its lists of {'bbox', 'landmarks', 'score'},
+    int32 frame coordinates."""
+
+    def __init__(self, checkpoint=None, tile=640, overlap=0.2, zoom=1.0, full_frame=True, short_side=416, edge=0.0, metric='iou',
+                 device=None, **model_kw):
+        from . import tiles
+        if _is_device_list(device):
+            raise ValueError('`device`: TiledDetection does not offer fan-out over a device list yet; pass one device')
+        tiles.check_args(tile, overlap, zoom, metric, edge)
+        if full_frame and not short_side > 0:
+            raise ValueError('`short_side` must be positive, not %r' % (short_side,))
+        self.device = device
+        self.tile, self.overlap, self.zoom, self.edge, self.metric = tile, overlap, zoom, edge, metric
+        self.full_frame, self.short_side = bool(full_frame), short_side
+        self.threshold = model_kw.pop('threshold', 0.5)
+        self.max_tiles = model_kw.pop('max_tiles', 256)
+        self.detection_cls = get_class_for_checkpoint('face-detection', checkpoint)
+        self._model_kw = model_kw
+        self.model = None
+
+    def __repr__(self):
+        return '<TiledDetection(%s)>' % self.detection_cls.__name__
+
+    def _ctx(self):
+        if self.model is None:
+            self.model = self.detection_cls(device=self.device, **self._model_kw)
+        return self.model.ctx
+
+    def upload(self, images):
+        return self._ctx().upload(images)
+
+    def _batch(self, frames):
+        """One resident batch -> list per frame of dicts."""
+        counts, boxes, lmks, scores = self.model.detect_tiles(
+            frames, self.tile, self.overlap, self.zoom, self.threshold, self.short_side if self.full_frame else None, self.edge,
+            self.metric, self.max_tiles)
+        b = np.around(boxes).astype(np.int32)
+        l = np.around(lmks).astype(np.int32)
+        return results.detections(counts, b, l, scores, lazy=self._model_kw.get('lazy_results') or None)
+
+    def _host_batch(self, ctx, images):
+        frames = ctx.upload(images)
+        try:
+            return self._batch(frames)
+        finally:
+            frames.free()
+
+    def __call__(self, images):
+        ctx = self._ctx()
+        if isinstance(images, lib.Frames):
+            return self._batch(images)
+        if isinstance(images, ShardedFrames):
+            raise ValueError('`device`: TiledDetection does not offer fan-out over a device list yet; pass one device')
+        if isinstance(images, np.ndarray):
+            if images.ndim == 3:
+                return self._host_batch(ctx, images[None])[0]
+            return self._host_batch(ctx, images)
+        _resident_list(images)                                       # all resident or none
+        out = [None] * len(images)
+        by_size = {}
+        for i, im in enumerate(images):
+            if isinstance(im, lib.Frames):
+                out[i] = self._batch(im)[0]
+            else:
+                by_size.setdefault(np.asarray(im).shape[:2], []).append(i)
+        for idx in by_size.values():                                 # one batch per size, answers back in input order
+            for i, dets in zip(idx, self._host_batch(ctx, np.stack([np.asarray(images[i]) for i in idx]))):
+                out[i] = dets
+        return out
+
+
 class Recognition:
 
     def __init__(self, checkpoint=None, device=None, lazy=False, **model_kw):

@@ -74,6 +74,7 @@ SIGNATURES = {
     'ta_frames_to_yuv': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     'ta_yuv_convert_samples': (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     'ta_frames_combine': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t]),
+    'ta_frames_tiles': (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, P(c_void_p)]),
     'ta_jpeg_coefficients': (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, C.c_int64, C.c_char_p, c_int]),
     'ta_jpeg_decode': (c_int, [c_void_p, P(c_void_p), P(c_size_t), c_int, c_int, c_int, P(c_void_p), P(C.c_int32),
                                P(C.c_int32)]),
@@ -99,6 +100,8 @@ SIGNATURES = {
                                   c_void_p, P(C.c_int32)]),
     'ta_retinaface_postprocess': (c_int, [c_void_p, P(c_void_p), c_int, c_int, c_int, c_float, c_float, c_int,
                                           c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
+    'ta_detections_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_float,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -203,6 +206,16 @@ COMBINE_DT = np.dtype([('frame', '<i4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<
                        ('mask_kind', '<i4'), ('mask_value', '<i4'), ('mask_frame', '<i4'), ('mask_x', '<i4'), ('mask_y', '<i4'),
                        ('mask_band', '<i4')])
 assert COMBINE_DT.itemsize == 72
+
+# ta_tile, ta_merge_group (include/terran_amd.h); MERGE_MAX_PER_FRAME: the candidates ta_detections_merge takes per frame
+TILE_DT = np.dtype([('frame', '<i4'), ('y', '<i4'), ('x', '<i4')])
+assert TILE_DT.itemsize == 12
+MERGE_GROUP_DT = np.dtype([('frame', '<i4'), ('first', '<i4'), ('count', '<i4'), ('ox', '<f4'), ('oy', '<f4'), ('zoom', '<f4'),
+                           ('x0', '<f4'), ('y0', '<f4'), ('x1', '<f4'), ('y1', '<f4'), ('interior', '<i4')])
+assert MERGE_GROUP_DT.itemsize == 44
+MERGE_IOU, MERGE_IOS = 0, 1
+MERGE_METRICS = {'iou': MERGE_IOU, 'ios': MERGE_IOS}
+MERGE_MAX_PER_FRAME = 16384
 
 # ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
 COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
@@ -614,6 +627,44 @@ class Context:
     def free_pinned(self, ptr):
         if getattr(self, 'h', None):
             self.lib.ta_host_free(self.h, c_void_p(ptr))
+
+    def frames_tiles(self, src, tiles, th, tw):
+        """ta_frames_tiles: `tiles`, a TILE_DT array (frame, y, x), cut out of the resident batch `src` in one launch -> a NEW
+        resident Frames batch (n, th, tw, 3), or None for no tiles."""
+        tiles, p, n = _records(tiles, TILE_DT)
+        hd = c_void_p()
+        self.check(self.lib.ta_frames_tiles(self.h, src.h, p, n, int(th), int(tw), C.byref(hd)))
+        return Frames(self, handle=hd) if hd.value else None
+
+    def detections_merge(self, groups, n_frames, boxes, landmarks, scores, nms_thr, metric=MERGE_IOU, edge=0.0, capacity=None):
+        """ta_detections_merge: candidates of tiles (`groups`, a MERGE_GROUP_DT array sorted by frame) -> (counts (n_frames,)
+        int32, boxes (T, 4), landmarks (T, 5, 2), scores (T,) float32, source (T,) int32 candidate rows): mapped to frame
+        coordinates, cut faces dropped, ordered and suppressed across tiles, frames concatenated.  `capacity`: the first
+        size of the output arrays (tests); a short one is retried with what the call asks for."""
+        groups, gp, ng = _records(groups, MERGE_GROUP_DT)
+        boxes = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 4)
+        landmarks = np.ascontiguousarray(landmarks, dtype=np.float32).reshape(-1, 5, 2)
+        scores = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+        c = len(scores)
+        if len(boxes) != c or len(landmarks) != c:
+            raise ValueError('detections_merge: %d boxes, %d landmarks, %d scores' % (len(boxes), len(landmarks), c))
+        n_frames = int(n_frames)
+        counts = np.zeros(max(n_frames, 1), np.int32)
+        cap = c if capacity is None else int(capacity)
+        while True:
+            ob, ol = np.empty((max(cap, 1), 4), np.float32), np.empty((max(cap, 1), 5, 2), np.float32)
+            osc, src = np.empty(max(cap, 1), np.float32), np.empty(max(cap, 1), np.int32)
+            req = C.c_int32(0)
+            rc = self.lib.ta_detections_merge(self.h, gp, ng, n_frames, ptr(boxes), ptr(landmarks), ptr(scores), c, float(nms_thr),
+                                              int(metric), float(edge), cap, ptr(counts), ptr(ob), ptr(ol), ptr(osc), ptr(src),
+                                              C.byref(req))
+            if rc == E_CAPACITY and req.value > cap:
+                cap = int(req.value)
+                continue
+            self.check(rc)
+            break
+        t = int(counts[:n_frames].sum())
+        return counts[:n_frames], ob[:t], ol[:t], osc[:t], src[:t]
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -45,6 +45,48 @@ class RetinaFace(runtime.RangeFallback):
         total = int(counts.sum())
         return counts, boxes[:total], lmks[:total], scores[:total]
 
+    def detect_tiles(self, frames, tile, overlap, zoom=1.0, threshold=0.5, full_frame_short_side=None, edge=0.0, metric='iou',
+                     max_tiles=256):
+        """Sliced inference on resident `frames` (lib.Frames, one size): every frame is cut into overlapping tiles
+        (`tiles.tile_grid`), each tile -- resized by `zoom` exactly as `Detection` resizes a cropped image -- goes through
+        `detect_arrays`, at most `max_tiles` at a time, optionally with a pass over the whole frames at
+        `full_frame_short_side`, and one `ta_detections_merge` maps everything back and suppresses across tiles (`edge`,
+        `metric`: include/terran_amd.h).  -> (counts (N,) int32, boxes (T,4), landmarks (T,5,2), scores (T,)) float32 in
+        frame coordinates, frames concatenated."""
+        from . import tiles as tl
+        metric = tl.check_args(tile, overlap, zoom, metric, edge, max_tiles)
+        ctx = self.ctx
+        n, H, W = frames.shape[:3]
+        if n == 0:
+            return np.zeros(0, np.int32), np.empty((0, 4), np.float32), np.empty((0, 5, 2), np.float32), np.empty(0, np.float32)
+        th, tw = tl.tile_shape(H, W, tile)
+        origins = tl.tile_grid(H, W, tile, overlap)
+        recs = tl.tile_records(n, origins)
+        parts = []
+        for lo in range(0, len(recs), int(max_tiles)):
+            cut = ctx.frames_tiles(frames, recs[lo:lo + int(max_tiles)], th, tw)
+            try:
+                if zoom != 1.0:
+                    big = cut.resize(int(th * zoom), int(tw * zoom), ctx=ctx)
+                    cut.free()
+                    cut = big
+                parts.append(self.detect_arrays(cut, threshold))
+            finally:
+                cut.free()
+        tile_counts = np.concatenate([p[0] for p in parts])
+        full_counts = full_scale = None
+        if full_frame_short_side is not None:
+            full_scale = full_frame_short_side / min(H, W)
+            whole = frames.resize(int(H * full_scale), int(W * full_scale), ctx=ctx)
+            try:
+                parts.append(self.detect_arrays(whole, threshold))
+            finally:
+                whole.free()
+            full_counts = parts[-1][0]
+        groups = tl.merge_groups(n, H, W, origins, th, tw, zoom, tile_counts, full_counts, full_scale)
+        boxes, lmks, scores = (np.concatenate([p[k] for p in parts]) for k in (1, 2, 3))
+        return ctx.detections_merge(groups, n, boxes, lmks, scores, self.nms_threshold, metric, edge)[:4]
+
     def call_frames(self, frames, threshold=0.5):
         """frames: lib.Frames (N,H,W,3) at network resolution, resident in HBM."""
         return results.detections(*self.detect_arrays(frames, threshold), lazy=self.lazy_results or None)
