@@ -859,6 +859,49 @@ int ta_openpose_run(ta_model* m, const ta_frames* frames, double scale, int capa
 int ta_openpose_group(ta_ctx* ctx, const float* pafs, const float* heatmaps, int n, int h, int w,
                       double scale, int capacity, int32_t* counts, int32_t* keypoints,
                       double* scores, int32_t* required);
+/* ---- tiled pose estimation: poses of tiles -> poses of their frames ---------------------------------------------------- */
+/* Candidates (host arrays: keypoints (C,18,3) int32 (x, y, present), what ta_openpose_run answers; scores (C,) float64,
+ * finite) come in GROUPS: the poses of one tile, or of one whole-frame pass, of one output frame.  Groups are sorted by
+ * frame and share no row; a row in no group is ignored.  Everything below is integer arithmetic, or one IEEE double
+ * multiply followed by a compare: the answer is defined bit for bit.  Per candidate:
+ *   present  joint j is present iff kp[j][2] != 0; a candidate with no present joint is dropped
+ *   map      a present joint becomes (x + ox, y + oy, kp[j][2]), an absent one (0, 0, 0); there is no zoom here, because
+ *            ta_openpose_run already divided by its scale; scores are unchanged
+ *   extent   bx0, bx1, by0, by1 = min and max over the mapped present joints; s2 = (bx1 - bx0 + 1) * (by1 - by0 + 1) as
+ *            int64; np = the number of present joints
+ *   edge     (edge > 0) it is dropped if bx0 < x0 + edge (left, bit 0), by0 < y0 + edge (top, bit 1), bx1 >= x1 - edge
+ *            (right, bit 2) or by1 >= y1 - edge (bottom, bit 3) on a side whose bit is set in `interior`: a body the tile
+ *            cut, which the overlapping neighbour sees more of
+ * Per frame the survivors are ordered by descending np, then descending score (-0 = +0), then ascending row: the most
+ * complete skeleton wins.  Two candidates a, b of one frame are DUPLICATES iff
+ *   - they come from different groups (the network's own assembly decided that two poses of one tile are two people:
+ *     a same-group pair is never compared), and
+ *   - shared = popcount(present_a & present_b) >= min_shared, and
+ *   - (double)matched >= agree * (double)shared, where matched counts the shared joints with
+ *     (double)(dx * dx + dy * dy) <= r2 * S, dx and dy in int64, r2 = radius * radius computed once in double,
+ *     S = (double)max(s2_a, s2_b): one double multiply on each side of each compare, in this order.
+ * The relation is symmetric.  Greedy suppression over the order: a candidate is kept iff no earlier KEPT candidate is its
+ * duplicate.  Outputs: the kept candidates per frame in that order, frames concatenated; counts[f] of frame f, the mapped
+ * keypoints, the unchanged scores, out_source = each one's candidate row.  Capacity protocol of ta_detections_merge: a
+ * short `capacity` gives TA_E_CAPACITY with *required and counts set and nothing else written.  Everything but the checks
+ * runs on the device; the suppression bit matrix lives in the context's scratch block (frames are processed in batches
+ * whose matrices fit 256 MiB, $TA_PM_MATRIX_BYTES overrides).
+ * TA_E_OVERFLOW: more than 16384 candidates in the groups of one frame (checked before any launch).  TA_E_INVALID:
+ * unsorted or overlapping groups, rows outside the arrays, a frame out of range, radius not finite or < 0, agree outside
+ * (0, 1], min_shared outside 1 .. 18, edge < 0, any |x|, |y| of a row in a group (present or not) or |ox|, |oy| at or
+ * above 2^22 -- below that bound s2 < 2^48 and dx * dx + dy * dy < 2^49 are exact in int64 and in double alike. */
+typedef struct ta_pose_group {
+  int32_t frame;          /* which output frame this group of candidates belongs to; groups come sorted by frame    */
+  int32_t first, count;   /* its candidates: rows first .. first+count-1 of the candidate arrays                    */
+  int32_t ox, oy;         /* frame = tile + origin                                                                  */
+  int32_t x0, y0, x1, y1; /* the group's rectangle in frame coordinates                                             */
+  int32_t interior;       /* bit 0 left, 1 top, 2 right, 3 bottom: that side of the rectangle lies inside the frame */
+} ta_pose_group;
+int ta_poses_merge(ta_ctx* ctx, const ta_pose_group* groups, int n_groups, int n_frames, const int32_t* keypoints,
+                   const double* scores, int n_candidates, double radius, double agree, int min_shared, int edge,
+                   int capacity, int32_t* counts, int32_t* out_keypoints, double* out_scores, int32_t* out_source,
+                   int32_t* required);
+
 /* Workload statistics of the last ta_openpose_run / ta_openpose_group on this context: heat-map peaks found over
  * all images and parts (wrapper.py:235-262) and limb connections accepted by the greedy matching (wrapper.py:335-366). */
 int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connections);

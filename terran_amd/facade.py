@@ -441,3 +441,83 @@ class Estimation:
                 new.append(row)
             out = new
         return out[0] if expanded else out
+
+
+class TiledEstimation:
+    """Pose estimation for frames whose people are too small for `Estimation`'s shrink to 184 pixels: every frame is cut
+    into overlapping `tile`-pixel tiles at its own resolution (times `zoom`), the pose network runs on each (`full_frame`:
+    and on the whole frame at `short_side`, for the people larger than a tile), and the skeletons are mapped back and the
+    duplicates across tiles suppressed on the device (`OpenPose.estimate_tiles`; `tiles.py` has the tiling,
+    include/terran_amd.h `edge`, `radius`, `agree` and `min_shared`, whose defaults come from the geometry and are not
+    tuned on data).  `max_tiles`: how many tiles go through the network in one call; 32 is a guess at what the activation
+    arena takes comfortably and is not measured.  Accepts what `TiledDetection` accepts on one device and returns
+    `Estimation`'s lists of {'keypoints': int32 (18, 3), 'score': float64} in frame coordinates."""
+
+    def __init__(self, checkpoint=None, tile=368, overlap=0.25, zoom=1.0, full_frame=True, short_side=184, edge=0, radius=0.1,
+                 agree=0.5, min_shared=3, device=None, max_tiles=32, **model_kw):
+        from . import tiles
+        if _is_device_list(device):
+            raise ValueError('`device`: TiledEstimation does not offer fan-out over a device list yet; pass one device')
+        tiles.check_pose_args(tile, overlap, zoom, edge, radius, agree, min_shared, max_tiles)
+        self.max_tiles = int(max_tiles)
+        if full_frame and not short_side > 0:
+            raise ValueError('`short_side` must be positive, not %r' % (short_side,))
+        self.device = device
+        self.tile, self.overlap, self.zoom, self.edge = tile, overlap, zoom, edge
+        self.radius, self.agree, self.min_shared = radius, agree, min_shared
+        self.full_frame, self.short_side = bool(full_frame), short_side
+        self.estimation_cls = get_class_for_checkpoint('pose-estimation', checkpoint)
+        self._model_kw = model_kw
+        self.model = None
+
+    def __repr__(self):
+        return '<TiledEstimation(%s)>' % self.estimation_cls.__name__
+
+    def _ctx(self):
+        if self.model is None:
+            self.model = self.estimation_cls(device=self.device, short_side=self.short_side, **self._model_kw)
+        return self.model.ctx
+
+    def upload(self, images):
+        return self._ctx().upload(images)
+
+    def _batch(self, frames):
+        """One resident batch -> list per frame of dicts."""
+        counts, kp, sc = self.model.estimate_tiles(
+            frames, self.tile, self.overlap, self.zoom, self.short_side if self.full_frame else None, self.edge, self.radius,
+            self.agree, self.min_shared, self.max_tiles)
+        out, o = [], 0
+        for c in counts:
+            out.append([{'keypoints': kp[i].copy(), 'score': np.float64(sc[i])} for i in range(o, o + int(c))])
+            o += int(c)
+        return out
+
+    def _host_batch(self, ctx, images):
+        frames = ctx.upload(images)
+        try:
+            return self._batch(frames)
+        finally:
+            frames.free()
+
+    def __call__(self, images):
+        ctx = self._ctx()
+        if isinstance(images, lib.Frames):
+            return self._batch(images)
+        if isinstance(images, ShardedFrames):
+            raise ValueError('`device`: TiledEstimation does not offer fan-out over a device list yet; pass one device')
+        if isinstance(images, np.ndarray):
+            if images.ndim == 3:
+                return self._host_batch(ctx, images[None])[0]
+            return self._host_batch(ctx, images)
+        _resident_list(images)                                       # all resident or none
+        out = [None] * len(images)
+        by_size = {}
+        for i, im in enumerate(images):
+            if isinstance(im, lib.Frames):
+                out[i] = self._batch(im)[0]
+            else:
+                by_size.setdefault(np.asarray(im).shape[:2], []).append(i)
+        for idx in by_size.values():                                 # one batch per size, answers back in input order
+            for i, poses in zip(idx, self._host_batch(ctx, np.stack([np.asarray(images[i]) for i in idx]))):
+                out[i] = poses
+        return out

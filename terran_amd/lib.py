@@ -102,6 +102,8 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_detections_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_float,
                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
+    'ta_poses_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_int, c_int,
+                               c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -216,6 +218,10 @@ assert MERGE_GROUP_DT.itemsize == 44
 MERGE_IOU, MERGE_IOS = 0, 1
 MERGE_METRICS = {'iou': MERGE_IOU, 'ios': MERGE_IOS}
 MERGE_MAX_PER_FRAME = 16384
+# ta_pose_group: the integer analogue for ta_poses_merge, with the same limit per frame
+POSE_GROUP_DT = np.dtype([('frame', '<i4'), ('first', '<i4'), ('count', '<i4'), ('ox', '<i4'), ('oy', '<i4'), ('x0', '<i4'), ('y0', '<i4'),
+                          ('x1', '<i4'), ('y1', '<i4'), ('interior', '<i4')])
+assert POSE_GROUP_DT.itemsize == 40
 
 # ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
 COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
@@ -665,6 +671,35 @@ class Context:
             break
         t = int(counts[:n_frames].sum())
         return counts[:n_frames], ob[:t], ol[:t], osc[:t], src[:t]
+
+    def poses_merge(self, groups, n_frames, keypoints, scores, radius=0.1, agree=0.5, min_shared=3, edge=0, capacity=None):
+        """ta_poses_merge: poses of tiles (`groups`, a POSE_GROUP_DT array sorted by frame; keypoints (C, 18, 3) int32, scores (C,)
+        float64) -> (counts (n_frames,) int32, keypoints (T, 18, 3) int32, scores (T,) float64, source (T,) int32 candidate
+        rows): mapped to frame coordinates, cut bodies dropped, ordered and the duplicates across tiles suppressed, frames
+        concatenated.  `capacity`: the first size of the output arrays (tests); a short one is retried with what the call asks
+        for."""
+        groups, gp, ng = _records(groups, POSE_GROUP_DT)
+        keypoints = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, 18, 3)
+        scores = np.ascontiguousarray(scores, dtype=np.float64).reshape(-1)
+        c = len(scores)
+        if len(keypoints) != c:
+            raise ValueError('poses_merge: %d keypoint rows, %d scores' % (len(keypoints), c))
+        n_frames = int(n_frames)
+        counts = np.zeros(max(n_frames, 1), np.int32)
+        cap = c if capacity is None else int(capacity)
+        while True:
+            okp = np.empty((max(cap, 1), 18, 3), np.int32)
+            osc, src = np.empty(max(cap, 1), np.float64), np.empty(max(cap, 1), np.int32)
+            req = C.c_int32(0)
+            rc = self.lib.ta_poses_merge(self.h, gp, ng, n_frames, ptr(keypoints), ptr(scores), c, float(radius), float(agree),
+                                         int(min_shared), int(edge), cap, ptr(counts), ptr(okp), ptr(osc), ptr(src), C.byref(req))
+            if rc == E_CAPACITY and req.value > cap:
+                cap = int(req.value)
+                continue
+            self.check(rc)
+            break
+        t = int(counts[:n_frames].sum())
+        return counts[:n_frames], okp[:t], osc[:t], src[:t]
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -28,7 +28,8 @@ def _unpack(counts, kp, sc):
     return out
 
 
-def _run(ctx, fn, n):
+def _run_arrays(ctx, fn, n):
+    """-> (counts (n,) int32, keypoints (T, 18, 3) int32, scores (T,) float64), the capacity grown until the call fits."""
     counts = np.zeros(max(n, 1), np.int32)
     cap = max(64, 16 * n)
     while True:
@@ -40,11 +41,16 @@ def _run(ctx, fn, n):
             cap = int(req.value)
             continue
         ctx.check(rc)
-        out = _unpack(counts[:n], kp, sc)
-        over = [i for i, r in enumerate(out) if r is None]
-        if over:
-            raise PoseOverflow(ctx.last_error() + '; images %s' % over, out, over)
-        return out
+        return counts[:n], kp, sc
+
+
+def _run(ctx, fn, n):
+    counts, kp, sc = _run_arrays(ctx, fn, n)
+    out = _unpack(counts, kp, sc)
+    over = [i for i, r in enumerate(out) if r is None]
+    if over:
+        raise PoseOverflow(ctx.last_error() + '; images %s' % over, out, over)
+    return out
 
 
 class OpenPose(runtime.RangeFallback):
@@ -71,6 +77,67 @@ class OpenPose(runtime.RangeFallback):
         finally:
             if resized is not frames:
                 resized.free()
+
+    def _estimate_arrays(self, frames, scale):
+        """One `ta_openpose_run` on resident frames at network resolution -> (counts, keypoints, scores) trimmed to the poses
+        found; TA_E_RANGE falls back as in `call_frames`."""
+        n = frames.shape[0]
+        counts, kp, sc = self._with_fallback(lambda model: _run_arrays(self.ctx, lambda cap, *a: self.ctx.lib.ta_openpose_run(
+            model.h, frames.h, float(scale), cap, *a), n))
+        if (counts < 0).any():
+            raise PoseOverflow(self.ctx.last_error(), None, np.nonzero(counts < 0)[0].tolist())
+        t = int(counts.sum())
+        return counts.copy(), kp[:t], sc[:t]
+
+    def estimate_tiles(self, frames, tile, overlap, zoom=1.0, full_frame_short_side=None, edge=0, radius=0.1, agree=0.5, min_shared=3,
+                       max_tiles=32):
+        """Sliced inference on resident `frames` (lib.Frames, one size): every frame is cut into overlapping tiles
+        (`tiles.tile_grid`), at most `max_tiles` at a time; each chunk is resized to (int(th * zoom), int(tw * zoom)) when that
+        differs from the tile and goes through `ta_openpose_run` with scale = zoom, which answers in the un-zoomed tile's
+        pixels; optionally one pass over the whole frames is made exactly as `call_frames` makes it, at
+        `full_frame_short_side`; one `ta_poses_merge` then maps every pose into its frame, drops the bodies a tile cut
+        (`edge`) and suppresses the duplicates across tiles (`radius`, `agree`, `min_shared`: include/terran_amd.h).
+        -> (counts (N,) int32, keypoints (T, 18, 3) int32, scores (T,) float64) in frame coordinates, frames concatenated.
+        `max_tiles` = 32 is a guess at what the activation arena takes comfortably; it is not measured."""
+        from . import tiles as tl
+        tl.check_pose_args(tile, overlap, zoom, edge, radius, agree, min_shared, max_tiles)
+        ctx = self.ctx
+        n, H, W = frames.shape[:3]
+        if n == 0:
+            return np.zeros(0, np.int32), np.empty((0, 18, 3), np.int32), np.empty(0, np.float64)
+        th, tw = tl.tile_shape(H, W, tile)
+        origins = tl.tile_grid(H, W, tile, overlap)
+        recs = tl.tile_records(n, origins)
+        zh, zw = int(th * zoom), int(tw * zoom)
+        if zh < 1 or zw < 1:
+            raise ValueError('`zoom` %r leaves nothing of a %d x %d tile' % (zoom, tw, th))
+        parts = []
+        for lo in range(0, len(recs), int(max_tiles)):
+            cut = ctx.frames_tiles(frames, recs[lo:lo + int(max_tiles)], th, tw)
+            big = None
+            try:
+                if (zh, zw) != (th, tw):
+                    big = cut.resize(zh, zw, ctx=ctx)
+                parts.append(self._estimate_arrays(big if big is not None else cut, zoom))
+            finally:
+                cut.free()
+                if big is not None:
+                    big.free()
+        tile_counts = np.concatenate([p[0] for p in parts])
+        full_counts = None
+        if full_frame_short_side is not None:
+            scale = full_frame_short_side / min(H, W)
+            nw, nh = int(W * scale), int(H * scale)
+            whole = frames if (nh, nw) == (H, W) else frames.resize(nh, nw, ctx=ctx)
+            try:
+                parts.append(self._estimate_arrays(whole, scale))
+            finally:
+                if whole is not frames:
+                    whole.free()
+            full_counts = parts[-1][0]
+        groups = tl.pose_groups(n, H, W, origins, th, tw, tile_counts, full_counts)
+        kp, sc = np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+        return ctx.poses_merge(groups, n, kp, sc, radius, agree, min_shared, edge)[:3]
 
     def call(self, images):
         """images: (N,H,W,3) uint8 RGB -> list[N] of list[{'keypoints': int32 (18,3), 'score': float64}],

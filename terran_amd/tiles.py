@@ -129,3 +129,59 @@ def merge_groups(n_frames, height, width, origins, th, tw, zoom, tile_counts, fu
         w['zoom'] = full_scale
         w['x1'], w['y1'] = width, height
     return g.reshape(-1)
+
+
+def check_pose_args(tile, overlap, zoom=1.0, edge=0, radius=0.1, agree=0.5, min_shared=3, max_tiles=32):
+    """The checks `estimate_tiles` and `TiledEstimation` share: ValueError naming the argument."""
+    th, tw = _pair(tile, 'tile')
+    if int(th) != th or int(tw) != tw or th < 1 or tw < 1:
+        raise ValueError('`tile` must be a positive int or a pair of them, not %r' % (tile,))
+    overlap_pixels(tile, overlap)
+    if not (isinstance(zoom, (int, float, np.integer, np.floating)) and math.isfinite(zoom) and zoom > 0):
+        raise ValueError('`zoom` must be a positive number, not %r' % (zoom,))
+    if not (isinstance(edge, (int, np.integer)) and not isinstance(edge, bool) and edge >= 0):
+        raise ValueError('`edge` must be an int of at least 0 (pixels), not %r' % (edge,))
+    if not (isinstance(radius, (int, float, np.integer, np.floating)) and math.isfinite(radius) and radius >= 0):
+        raise ValueError('`radius` must be a finite number of at least 0, not %r' % (radius,))
+    if not (isinstance(agree, (int, float, np.integer, np.floating)) and 0 < agree <= 1):
+        raise ValueError('`agree` must lie in (0, 1], not %r' % (agree,))
+    if not (isinstance(min_shared, (int, np.integer)) and not isinstance(min_shared, bool) and 1 <= min_shared <= 18):
+        raise ValueError('`min_shared` must be an int in 1 .. 18, not %r' % (min_shared,))
+    if int(max_tiles) < 1:
+        raise ValueError('`max_tiles` must be at least 1, not %r' % (max_tiles,))
+
+
+def pose_groups(n_frames, height, width, origins, th, tw, tile_counts, full_counts=None):
+    """The POSE_GROUP_DT records of a batch of `n_frames` frames of height x width: `merge_groups` in integers.
+
+    The candidate arrays hold the poses of every tile, frame-major (frame 0's tiles in `origins` order, frame 1's, ...:
+    `tile_counts` per tile), in the coordinates of the un-zoomed tile (`ta_openpose_run` divides by its scale); then, if
+    `full_counts` is given, those of a whole-frame pass (`full_counts` per frame), already in frame coordinates.  A tile's
+    rectangle is its own, and a side of it is interior when it does not lie on the frame's border; a whole-frame pass is
+    one more group per frame with origin 0, the rectangle (0, 0, width, height) and no interior side.  The records come
+    sorted by frame."""
+    origins = np.asarray(origins, np.int32).reshape(-1, 2)
+    nt = len(origins)
+    tile_counts = np.asarray(tile_counts, np.int64).reshape(-1)
+    if len(tile_counts) != n_frames * nt:
+        raise ValueError('pose_groups: %d tile counts for %d frames of %d tiles' % (len(tile_counts), n_frames, nt))
+    per = nt + (full_counts is not None)
+    g = np.zeros((n_frames, per), lib.POSE_GROUP_DT)
+    g['frame'] = np.arange(n_frames, dtype=np.int32)[:, None]
+    first = np.concatenate([[0], np.cumsum(tile_counts)])
+    t = g[:, :nt]
+    t['first'] = first[:-1].reshape(n_frames, nt)
+    t['count'] = tile_counts.reshape(n_frames, nt)
+    y, x = origins[:, 0][None], origins[:, 1][None]
+    t['ox'], t['oy'] = x, y
+    t['x0'], t['y0'], t['x1'], t['y1'] = x, y, x + tw, y + th
+    t['interior'] = (x > 0) * 1 + (y > 0) * 2 + (x + tw < width) * 4 + (y + th < height) * 8
+    if full_counts is not None:
+        full_counts = np.asarray(full_counts, np.int64).reshape(-1)
+        if len(full_counts) != n_frames:
+            raise ValueError('pose_groups: the whole-frame pass needs one count per frame')
+        w = g[:, nt]
+        w['first'] = first[-1] + np.concatenate([[0], np.cumsum(full_counts)])[:-1]
+        w['count'] = full_counts
+        w['x1'], w['y1'] = width, height
+    return g.reshape(-1)
