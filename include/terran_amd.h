@@ -902,6 +902,44 @@ int ta_poses_merge(ta_ctx* ctx, const ta_pose_group* groups, int n_groups, int n
                    int capacity, int32_t* counts, int32_t* out_keypoints, double* out_scores, int32_t* out_source,
                    int32_t* required);
 
+/* ---- whose face is this body's?  faces of frames <-> skeletons of frames ------------------------------------------------ */
+/* Host arrays, frames concatenated: face_counts / pose_counts (n_frames,) int32; boxes (n_faces, 4) int32 (x0, y0, x1, y1),
+ * the detector's bbox; keypoints (n_poses, 18, 3) int32 (x, y, present), what ta_openpose_run and ta_poses_merge answer.
+ * All arithmetic is integer, so the answer is defined bit for bit.  Per frame, for its face f and pose p (indices local to
+ * the frame):
+ *   head      joints 0, 14, 15, 16, 17 (nose, both eyes, both ears); a joint is present iff its third value is != 0, and
+ *             the x, y of an absent joint are ignored whatever they hold; n = the number of present head joints; a pose with
+ *             n == 0 links to nothing
+ *   box       w = x1 - x0, h = y1 - y0; a box with w < 0 or h < 0 contains nothing (its face links to nothing; no error);
+ *             mx = (w * margin_permille) / 1000, my = (h * margin_permille) / 1000 in int64, truncating (both >= 0); a
+ *             joint is inside iff x0 - mx <= x <= x1 + mx and y0 - my <= y <= y1 + my, inclusive on all four sides
+ *   pair      inside = the present head joints inside; the pair QUALIFIES iff inside >= min_inside and 2 * inside >= n
+ *             (a neighbour whose one ear pokes into the box stays out)
+ *   cost      cx = x0 + x1, cy = y0 + y1 (doubled coordinates); S = the sum over ALL present head joints of
+ *             (2x - cx)^2 + (2y - cy)^2 in int64; cost = S * (60 / n), 60 / n being 60, 30, 20, 15 or 12: 60 x the mean
+ *             squared distance to the box centre as one int64
+ *   range     every |x|, |y| and box coordinate is below 2^22, so |2x - cx| < 2^24, a joint adds less than 2^49,
+ *             S < n * 2^49 and cost < 60 * 2^49 < 2^55: exact in int64, which the device keeps throughout (costs pass
+ *             2^53; no float appears anywhere)
+ *   match     the qualifying pairs of a frame are ordered by (cost, f, p) ascending, a strict total order, and walked in that
+ *             order: a pair is linked iff neither its face nor its pose is linked yet
+ * Outputs: pose_of_face (n_faces,) the frame-local pose index or -1; face_of_pose (n_poses,) the frame-local face index or
+ * -1; links (n_frames,) the pairs linked per frame, may be NULL; rounds, may be NULL: the device commits every mutually
+ * best pair (the cheapest free pair of its face by (cost, p) and of its pose by (cost, f)) round after round until a round
+ * commits nothing, which gives the walk's answer; a frame runs its committing rounds and that silent one, *rounds is the
+ * largest number over the frames (1 when nothing links, 0 for n_frames == 0).  The answer depends on nothing the device
+ * schedules and on nothing but the frame's own faces and poses.  The matrix of qualifying pairs, one bit a pair and once
+ * per side, lives in the context's scratch block (frames are processed in batches whose matrices fit 256 MiB,
+ * $TA_FL_MATRIX_BYTES overrides); nothing else grows with n_faces * n_poses.
+ * Checked on the host before any launch, outputs untouched on failure.  TA_E_OVERFLOW: more than 16384 faces or more than
+ * 16384 poses in one frame, the per-frame limit of the two merge calls that feed this one.  TA_E_INVALID: a negative count;
+ * counts that do not sum to n_faces / n_poses; a NULL array that has rows; margin_permille outside 0 .. 4000; min_inside
+ * outside 1 .. 5; any box coordinate, or any x, y of any of the 18 joints of a row (present or not), at or above 2^22 in
+ * size.  n_frames == 0 and frames with no faces or no poses succeed. */
+int ta_faces_poses_link(ta_ctx* ctx, int n_frames, const int32_t* face_counts, const int32_t* boxes, int n_faces,
+                        const int32_t* pose_counts, const int32_t* keypoints, int n_poses, int margin_permille,
+                        int min_inside, int32_t* pose_of_face, int32_t* face_of_pose, int32_t* links, int32_t* rounds);
+
 /* Workload statistics of the last ta_openpose_run / ta_openpose_group on this context: heat-map peaks found over
  * all images and parts (wrapper.py:235-262) and limb connections accepted by the greedy matching (wrapper.py:335-366). */
 int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connections);

@@ -12,6 +12,7 @@ from .retinaface import RetinaFace                                # noqa: F401
 from .arcface import ArcFace                                      # noqa: F401
 from .openpose import OpenPose, PoseOverflow                      # noqa: F401
 from .gallery import FaceGallery, cluster_faces                   # noqa: F401
+from .link import link_faces_poses, head_boxes                    # noqa: F401
 
 face_detection = Detection(lazy=True)
 extract_features = Recognition(lazy=True)

@@ -104,6 +104,8 @@ SIGNATURES = {
                                     c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_poses_merge': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_double, c_double, c_int, c_int, c_int,
                                c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
+    'ta_faces_poses_link': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, P(C.c_int32)]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -222,6 +224,8 @@ MERGE_MAX_PER_FRAME = 16384
 POSE_GROUP_DT = np.dtype([('frame', '<i4'), ('first', '<i4'), ('count', '<i4'), ('ox', '<i4'), ('oy', '<i4'), ('x0', '<i4'), ('y0', '<i4'),
                           ('x1', '<i4'), ('y1', '<i4'), ('interior', '<i4')])
 assert POSE_GROUP_DT.itemsize == 40
+# ta_faces_poses_link: the faces, and the poses, it takes per frame
+LINK_MAX_PER_FRAME = 16384
 
 # ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
 COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
@@ -700,6 +704,24 @@ class Context:
             break
         t = int(counts[:n_frames].sum())
         return counts[:n_frames], okp[:t], osc[:t], src[:t]
+
+    def faces_poses_link(self, face_counts, boxes, pose_counts, keypoints, margin_permille=250, min_inside=1):
+        """ta_faces_poses_link: per frame (face_counts, pose_counts (n_frames,); boxes (F, 4) int32; keypoints (P, 18, 3) int32, frames
+        concatenated) the greedy one-to-one link of faces and skeletons by head joints inside the widened box -> (pose_of_face (F,)
+        int32, face_of_pose (P,) int32, frame-local indices or -1; links (n_frames,) int32; the rounds the call ran)."""
+        fc = np.ascontiguousarray(face_counts, dtype=np.int32).reshape(-1)
+        pc = np.ascontiguousarray(pose_counts, dtype=np.int32).reshape(-1)
+        if len(fc) != len(pc):
+            raise ValueError('faces_poses_link: %d face counts, %d pose counts' % (len(fc), len(pc)))
+        boxes = np.ascontiguousarray(boxes, dtype=np.int32).reshape(-1, 4)
+        keypoints = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, 18, 3)
+        nf, npose, n = len(boxes), len(keypoints), len(fc)
+        pof, fop, links = np.empty(max(nf, 1), np.int32), np.empty(max(npose, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        rounds = C.c_int32(0)
+        self.check(self.lib.ta_faces_poses_link(self.h, n, ptr(fc) if n else None, ptr(boxes) if nf else None, nf, ptr(pc) if n else None,
+                                                ptr(keypoints) if npose else None, npose, int(margin_permille), int(min_inside), ptr(pof),
+                                                ptr(fop), ptr(links), C.byref(rounds)))
+        return pof[:nf], fop[:npose], links[:n], int(rounds.value)
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)
