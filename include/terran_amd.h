@@ -940,6 +940,46 @@ int ta_faces_poses_link(ta_ctx* ctx, int n_frames, const int32_t* face_counts, c
                         const int32_t* pose_counts, const int32_t* keypoints, int n_poses, int margin_permille,
                         int min_inside, int32_t* pose_of_face, int32_t* face_of_pose, int32_t* links, int32_t* rounds);
 
+/* ---- which skeleton of an earlier frame is this one?  skeletons followed over the frames of a sequence -------------------- */
+/* Host arrays, sequences and frames concatenated: frames_per_sequence (n_sequences,) int32 -- independent streams (cameras,
+ * shots of a clip), nothing links across a sequence boundary; history_frames (n_sequences,) int32, 0 .. the sequence's frame
+ * count: the first h frames of a sequence are history of earlier calls, their skeletons can be predecessors but look for none;
+ * pose_counts (n_frames,) int32; keypoints (n_poses, 18, 3) int32 (x, y, present) as above: a joint is present iff its third
+ * value is != 0, the x, y of an absent joint are ignored; closed (n_poses,) uint8, may be NULL: nonzero = this skeleton
+ * already has a successor (from an earlier call) and cannot be a predecessor.  All arithmetic is integer, so the answer is
+ * defined bit for bit.
+ *   pairs     skeleton a of frame ta and skeleton b of frame tb, both frames in the same sequence, tb not a history frame,
+ *             g = tb - ta with 1 <= g <= max_gap + 1
+ *   shared    the joints present in both; s = their number
+ *   size      per skeleton the larger of (max x - min x) and (max y - min y) over its present joints (0 with no joint or one);
+ *             M = the larger size of the two
+ *   D         the sum over the shared joints of dx^2 + dy^2, in int64
+ *   pair      QUALIFIES iff s >= min_shared and D * 1 000 000 <= radius_permille^2 * g * M^2 * s: the mean squared displacement
+ *             of the shared joints is at most (radius * M)^2 * g; the bound grows with the gap as a random walk's does
+ *   cost      D * (12 252 240 / s), one int64; 12 252 240 = lcm(1 .. 18), so this is exactly that multiple of the mean squared
+ *             displacement
+ *   range     every |x|, |y| of every joint of a row, present or not, is below 2^14 (checked), so |dx| < 2^15, dx^2 + dy^2 <
+ *             2^31, D < 18 * 2^31 < 2^36; D * 10^6 < 2^56; the right side is below 2^20 * 2^5 * 2^30 * 2^5 = 2^60; the cost is
+ *             below 2^36 * 2^24 = 2^60: exact in int64, which the device keeps throughout (no float appears anywhere)
+ *   match     the frames of a sequence are taken in ascending order.  At frame t the candidates are the qualifying pairs whose
+ *             b lies in t and whose a is OPEN: not closed on input and without a successor so far.  They are ordered by
+ *             (cost, g, a, b) ascending, a and b as global rows: a strict total order; they are walked in that order and a pair
+ *             is linked iff a has no successor and b no predecessor yet
+ * Outputs: prev (n_poses,) int32, the global row of the predecessor or -1 (history rows always -1); root (n_poses,) int32, the
+ * row reached by following prev to its end (a row that links to nothing is its own root); links (n_frames,) int32, may be
+ * NULL: the links made into each frame.  The device commits every mutually best pair of a frame round after round, which gives
+ * the walk's answer; it depends on nothing the device schedules.  The matrix of qualifying pairs, one bit a pair and once per
+ * side, lives in the context's scratch block (frames are processed in batches whose matrices fit 256 MiB, $TA_PT_MATRIX_BYTES
+ * overrides; one frame at the limit with max_gap 30 takes about 130 MB).
+ * Checked on the host before any launch, outputs untouched on failure.  TA_E_OVERFLOW: more than 4096 skeletons in one frame.
+ * TA_E_INVALID: a negative count; frames_per_sequence that does not sum to n_frames, or pose_counts that does not sum to
+ * n_poses; history_frames out of range; a NULL array that has rows; radius_permille outside 1 .. 1000; min_shared outside
+ * 1 .. 18; max_gap outside 0 .. 30; any x, y of any joint of a row at or above 2^14 in size.  Zero sequences, empty frames
+ * and sequences that are all history succeed. */
+int ta_poses_track(ta_ctx* ctx, int n_sequences, const int32_t* frames_per_sequence, const int32_t* history_frames,
+                   int n_frames, const int32_t* pose_counts, const int32_t* keypoints, const uint8_t* closed, int n_poses,
+                   int radius_permille, int min_shared, int max_gap, int32_t* prev, int32_t* root, int32_t* links);
+
 /* Workload statistics of the last ta_openpose_run / ta_openpose_group on this context: heat-map peaks found over
  * all images and parts (wrapper.py:235-262) and limb connections accepted by the greedy matching (wrapper.py:335-366). */
 int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connections);

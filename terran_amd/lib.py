@@ -106,6 +106,8 @@ SIGNATURES = {
                                c_void_p, c_void_p, c_void_p, c_void_p, P(C.c_int32)]),
     'ta_faces_poses_link': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, P(C.c_int32)]),
+    'ta_poses_track': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -226,6 +228,8 @@ POSE_GROUP_DT = np.dtype([('frame', '<i4'), ('first', '<i4'), ('count', '<i4'), 
 assert POSE_GROUP_DT.itemsize == 40
 # ta_faces_poses_link: the faces, and the poses, it takes per frame
 LINK_MAX_PER_FRAME = 16384
+# ta_poses_track: the skeletons it takes per frame
+TRACK_MAX_PER_FRAME = 4096
 
 # ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
 COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
@@ -722,6 +726,28 @@ class Context:
                                                 ptr(keypoints) if npose else None, npose, int(margin_permille), int(min_inside), ptr(pof),
                                                 ptr(fop), ptr(links), C.byref(rounds)))
         return pof[:nf], fop[:npose], links[:n], int(rounds.value)
+
+    def poses_track(self, frames_per_sequence, history_frames, pose_counts, keypoints, closed=None, radius_permille=100, min_shared=3, max_gap=0):
+        """ta_poses_track: skeletons followed over the frames of independent sequences (frames_per_sequence, history_frames
+        (n_sequences,); pose_counts (n_frames,); keypoints (P, 18, 3) int32; closed (P,) uint8 or None, all concatenated) -> (prev (P,)
+        int32, the global row of each skeleton's predecessor or -1; root (P,) int32, the first row of its track; links (n_frames,)
+        int32)."""
+        fps = np.ascontiguousarray(frames_per_sequence, dtype=np.int32).reshape(-1)
+        hist = np.ascontiguousarray(history_frames, dtype=np.int32).reshape(-1)
+        if len(fps) != len(hist):
+            raise ValueError('poses_track: %d sequences, %d history counts' % (len(fps), len(hist)))
+        pc = np.ascontiguousarray(pose_counts, dtype=np.int32).reshape(-1)
+        keypoints = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, 18, 3)
+        ns, n, npose = len(fps), len(pc), len(keypoints)
+        if closed is not None:
+            closed = np.ascontiguousarray(closed, dtype=np.uint8).reshape(-1)
+            if len(closed) != npose:
+                raise ValueError('poses_track: %d closed flags for %d skeletons' % (len(closed), npose))
+        prev, root, links = np.empty(max(npose, 1), np.int32), np.empty(max(npose, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        self.check(self.lib.ta_poses_track(self.h, ns, ptr(fps) if ns else None, ptr(hist) if ns else None, n, ptr(pc) if n else None,
+                                           ptr(keypoints) if npose else None, ptr(closed) if closed is not None and npose else None, npose,
+                                           int(radius_permille), int(min_shared), int(max_gap), ptr(prev), ptr(root), ptr(links)))
+        return prev[:npose], root[:npose], links[:n]
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -201,3 +201,114 @@ def face_tracking(*, video=None, max_age=None, min_hits=None, detector=None, ret
         raise ValueError('`detector` must be an instance of `terran.face.Detection`.')
     return FaceTracking(detector=detector, tracker=Sort(max_age=max_age, min_hits=min_hits,
                                                         return_unmatched=return_unmatched))
+
+
+# ---- skeletons ---------------------------------------------------------------------------------------------------------------
+# Not the reference's (it has no pose tracker): the rule of ta_poses_track (include/terran_amd.h), in integers and on the
+# device; what stays on the host is the bookkeeping between calls.
+_pose_ids = itertools.count()
+
+
+def reset_pose_track_ids(start=0):
+    """Restart the process-wide counter of skeleton track ids (tests / new video); the faces' counter is a separate one."""
+    global _pose_ids
+    _pose_ids = itertools.count(start)
+
+
+class PoseTracker:
+    """Follows the skeletons of one stream: `update(poses)` takes the next consecutive frames and writes pose['pose_track'].
+
+    A skeleton continues the cheapest open skeleton of the `max_gap + 1` frames before it whose shared joints moved, in the
+    mean square, at most (`radius` x the larger skeleton's size)^2 per frame of gap, with at least `min_shared` joints in common
+    (ta_poses_track states the rule to the bit); one that continues nothing starts a track, ids ascending in row order over all
+    trackers of the process.  The last `max_gap + 1` frames' keypoints, ids and successor flags are kept and prepended to the
+    next call as history, so a clip tracked in one call and in batches of any size gets the same ids.  `carry`: a tracked
+    skeleton that lacks one of these keys receives the value its track last carried -- the name that `identify` and
+    `link_faces_poses` gave a body stays when the person turns away."""
+
+    def __init__(self, max_gap=5, radius=0.1, min_shared=3, carry=('text', 'track', 'cluster'), ctx=None, device=None):
+        if isinstance(device, (list, tuple)):
+            raise ValueError('`device`: PoseTracker does not offer fan-out over a device list yet; pass one device')
+        self.max_gap, self.min_shared, self.carry = int(max_gap), int(min_shared), tuple(carry)
+        self.radius_permille = int(round(float(radius) * 1000))
+        self.ctx, self.device = ctx, device
+        self._history = []              # per kept frame: (keypoints (n, 18, 3) int32, ids (n,) int64, closed (n,) uint8)
+        self._carried = {}              # id -> {key: the value the track last carried}
+
+    def _context(self):
+        if self.ctx is None:
+            from . import runtime
+            self.ctx = runtime.get_context(self.device)
+        return self.ctx
+
+    def update(self, poses):
+        """poses: a list of lists of dicts, one per frame, or one frame's list of dicts -> the per-frame int64 id arrays (that
+        one array for the single-frame form)."""
+        poses = list(poses)
+        nested = [isinstance(v, (list, tuple)) for v in poses]
+        if any(nested) and not all(nested):
+            raise ValueError('poses must be one list of dicts, or one list of dicts per frame')
+        single = not any(nested)
+        frames = [poses] if single else [list(v) for v in poses]
+        hist = self._history
+        new_kp = [np.array([np.asarray(p['keypoints']).reshape(18, 3) for p in v], np.int32).reshape(-1, 18, 3) for v in frames]
+        kp = np.concatenate([h[0] for h in hist] + new_kp) if hist or new_kp else np.zeros((0, 18, 3), np.int32)
+        counts = np.array([len(h[0]) for h in hist] + [len(v) for v in frames], np.int32)
+        n_hist = int(counts[:len(hist)].sum())
+        closed = np.concatenate([h[2] for h in hist] + [np.zeros(len(kp) - n_hist, np.uint8)])
+        prev, root, _ = self._context().poses_track([len(counts)], [len(hist)], counts, kp, closed, self.radius_permille, self.min_shared,
+                                                    self.max_gap)
+        ids = np.concatenate([h[1] for h in hist] + [np.full(len(kp) - n_hist, -1, np.int64)])
+        for row in range(n_hist, len(kp)):              # a root lies in an earlier row, or is the row itself
+            r = int(root[row])
+            ids[row] = next(_pose_ids) if r == row else ids[r]
+        closed[prev[prev >= 0]] = 1
+        out, at = [], n_hist
+        for v in frames:
+            mine = ids[at:at + len(v)].copy()
+            for pose, k in zip(v, mine.tolist()):
+                pose['pose_track'] = k
+                kept = self._carried.setdefault(k, {})
+                for key in self.carry:
+                    if key in pose:
+                        kept[key] = pose[key]
+                    elif key in kept:
+                        pose[key] = kept[key]
+            out.append(mine)
+            at += len(v)
+        # what the next call can still link to: the last max_gap + 1 frames
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        keep = range(max(0, len(counts) - (self.max_gap + 1)), len(counts))
+        self._history = [(kp[starts[f]:starts[f + 1]].copy(), ids[starts[f]:starts[f + 1]].copy(), closed[starts[f]:starts[f + 1]].copy()) for f in keep]
+        live = set(int(k) for h in self._history for k in h[1])
+        self._carried = {k: v for k, v in self._carried.items() if k in live}     # an id that left the window never returns
+        return out[0] if single else out
+
+
+class PoseTracking:
+    """Drop-in for an `Estimation` / `TiledEstimation` object that adds a 'pose_track' field to every skeleton."""
+
+    def __init__(self, estimator=None, tracker=None):
+        self.estimator = estimator
+        self.tracker = tracker
+
+    def __call__(self, frames):
+        single = not isinstance(frames, (list, tuple)) and getattr(frames, 'ndim', 4) == 3
+        batch = [frames] if single else frames
+        per_frame = [list(v) for v in self.estimator(batch)]
+        self.tracker.update(per_frame)
+        return per_frame[0] if single else per_frame
+
+
+def pose_tracking(*, video=None, max_gap=None, estimator=None, **rule):
+    """Factory: a fifth of a second of frames for `max_gap` when a video (anything with `.framerate`) is given, else 5;
+    `rule` goes to `PoseTracker` (radius, min_shared, carry, ctx, device)."""
+    import terran_amd
+    from . import facade
+    if max_gap is None:
+        max_gap = video.framerate // 5 if video is not None else 5
+    if estimator is None:
+        estimator = terran_amd.pose_estimation
+    elif not isinstance(estimator, (facade.Estimation, facade.TiledEstimation)):
+        raise ValueError('`estimator` must be an instance of `Estimation` or `TiledEstimation`.')
+    return PoseTracking(estimator=estimator, tracker=PoseTracker(max_gap=max_gap, **rule))
