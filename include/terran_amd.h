@@ -980,6 +980,42 @@ int ta_poses_track(ta_ctx* ctx, int n_sequences, const int32_t* frames_per_seque
                    int n_frames, const int32_t* pose_counts, const int32_t* keypoints, const uint8_t* closed, int n_poses,
                    int radius_permille, int min_shared, int max_gap, int32_t* prev, int32_t* root, int32_t* links);
 
+/* ---- where is this person?  skeletons painted into resident frames as silhouettes, in place ----------------------------- */
+/* Host arrays, frames concatenated: pose_counts (n_frames,) int32 lists the FIRST n_frames frames of the batch (n_frames <= the
+ * batch's n; later frames are untouched); keypoints (n_poses, 18, 3) int32 (x, y, present) as above: a joint is present iff its
+ * third value is != 0, the x, y of an absent joint are ignored; rgba (n_poses, 4) uint8: ink r, g, b and alpha per pose;
+ * radius_permille: three ints, one per class.  All arithmetic is integer, so the answer is defined bit for bit.
+ *   size      M = the larger of (max x - min x) and (max y - min y) over the pose's present joints (0 with one joint); a pose
+ *             with no present joint paints nothing
+ *   classes   HEAD = 0, TORSO = 1, LIMB = 2; r_c = max(min_radius, M * radius_permille[c] / 1000), the product in int64, the
+ *             division truncating
+ *   joints    every present joint is a disc of its class's radius.  HEAD: joints 0, 14, 15, 16, 17; TORSO: 1, 2, 5, 8, 11;
+ *             LIMB: 3, 4, 6, 7, 9, 10, 12, 13
+ *   segments  each only if both its ends are present, a capsule of its class's radius.  HEAD: (0,1) (0,14) (14,16) (0,15)
+ *             (15,17); TORSO: (1,2) (1,5) (1,8) (1,11) (8,11); LIMB: (2,3) (3,4) (8,9) (9,10) (5,6) (6,7) (11,12) (12,13)
+ *   covered   pixel P = (px, py) by the segment A -> B of radius r, with d = B - A, L2 = d.d, p = P - A, t = p.d, all int64:
+ *             if t <= 0: p.p <= r^2; else if t >= L2: |P - B|^2 <= r^2; else cross^2 <= r^2 * L2 with cross = p.x d.y - p.y d.x.
+ *             Every comparison is inclusive.  A disc is the segment with A == B (L2 = 0, t = 0: the first case).  A pose covers
+ *             a pixel iff one of its discs or capsules does
+ *   range     every |x|, |y| of every joint of a row, present or not, is below 2^14 (checked) and a frame has at most 16384
+ *             pixels a side (checked), so |p|, |d| < 2^15, L2 < 2^31, |t| < 2^31, |cross| < 2^31, cross^2 < 2^62, r < 2^15 and
+ *             r^2 * L2 < 2^61: exact in int64, which the device keeps throughout (no float appears anywhere)
+ *   paint     clear != 0: every byte of the listed frames is first set to 0 (by this call's own writes: a pixel nobody covers
+ *             ends as 0).  Then the poses of a frame are applied in list order; a pixel is blended ONCE per pose that covers it,
+ *             however many of that pose's shapes do; per band with a = the pose's alpha
+ *                 v = in * (255 - a) + ink * a + 128;  out = ((v >> 8) + v) >> 8
+ *             which is ta_frames_draw's blend (TA_DRAW_BAR).  Alpha 255 replaces, alpha 0 changes nothing.  With clear == 0 a
+ *             listed frame with count 0 is not written at all, and no pixel outside a pose's coverage is written
+ * The answer depends on nothing the device schedules: a pixel is owned by one thread, which walks the frame's poses in order.
+ * Which poses a tile of pixels must look at is a tile x pose bit matrix in the context's scratch block (frames are processed in
+ * batches whose matrices fit 256 MiB, a single larger frame in runs of its poses; $TA_PP_MATRIX_BYTES overrides).
+ * Checked on the host before any launch, pixels untouched on failure.  TA_E_OVERFLOW: more than 16384 poses in one frame.
+ * TA_E_INVALID: a negative count; pose_counts that does not sum to n_poses; n_frames above the batch's n; a NULL array that has
+ * rows; a permille outside 0 .. 1000; min_radius outside 0 .. 4096; any x, y of any joint of a row at or above 2^14 in size; a
+ * frame side above 16384.  n_frames == 0 and n_poses == 0 succeed (with clear they just clear the listed frames). */
+int ta_poses_paint(ta_ctx* ctx, ta_frames* frames, int n_frames, const int32_t* pose_counts, const int32_t* keypoints,
+                   const uint8_t* rgba, int n_poses, const int32_t radius_permille[3], int min_radius, int clear);
+
 /* Workload statistics of the last ta_openpose_run / ta_openpose_group on this context: heat-map peaks found over
  * all images and parts (wrapper.py:235-262) and limb connections accepted by the greedy matching (wrapper.py:335-366). */
 int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connections);

@@ -108,6 +108,7 @@ SIGNATURES = {
                                     c_void_p, P(C.c_int32)]),
     'ta_poses_track': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_void_p]),
+    'ta_poses_paint': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -748,6 +749,24 @@ class Context:
                                            ptr(keypoints) if npose else None, ptr(closed) if closed is not None and npose else None, npose,
                                            int(radius_permille), int(min_shared), int(max_gap), ptr(prev), ptr(root), ptr(links)))
         return prev[:npose], root[:npose], links[:n]
+
+    def poses_paint(self, frames, pose_counts, keypoints, rgba, radius_permille=(90, 90, 50), min_radius=2, clear=False):
+        """ta_poses_paint: the skeletons of the first len(pose_counts) frames of the resident batch `frames` painted into it as
+        silhouettes, in place (pose_counts (n_frames,); keypoints (P, 18, 3) int32; rgba (P, 4) uint8 ink and alpha, concatenated;
+        radius_permille: head, torso, limb radius in thousandths of a skeleton's size; `clear`: the listed frames are zeroed
+        first).  Returns `frames`."""
+        pc = np.ascontiguousarray(pose_counts, dtype=np.int32).reshape(-1)
+        keypoints = np.ascontiguousarray(keypoints, dtype=np.int32).reshape(-1, 18, 3)
+        rgba = np.ascontiguousarray(rgba, dtype=np.uint8).reshape(-1, 4)
+        if len(rgba) != len(keypoints):
+            raise ValueError('poses_paint: %d inks for %d skeletons' % (len(rgba), len(keypoints)))
+        permille = np.ascontiguousarray(radius_permille, dtype=np.int32).reshape(-1)
+        if len(permille) != 3:
+            raise ValueError('poses_paint: radius_permille is (head, torso, limb), got %r' % (radius_permille,))
+        n, npose = len(pc), len(keypoints)
+        self.check(self.lib.ta_poses_paint(self.h, frames.h, n, ptr(pc) if n else None, ptr(keypoints) if npose else None,
+                                           ptr(rgba) if npose else None, npose, ptr(permille), int(min_radius), int(bool(clear))))
+        return frames
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -725,6 +725,289 @@ def filter_faces(frames, faces_per_frame, flt, margin=0.0, shape='box', ctx=None
     return frames
 
 
+# ---- whole people: silhouettes from skeletons --------------------------------------------------------------------------
+# ta_poses_paint (include/terran_amd.h states the rule to the bit): every present joint a disc, every connection a capsule,
+# their radii a share of the skeleton's size by class.  Not the reference's: it draws stick figures only.
+HEAD, TORSO, LIMB = 0, 1, 2
+SILHOUETTE_JOINT_CLASS = np.array([HEAD, TORSO, TORSO, LIMB, LIMB, TORSO, LIMB, LIMB, TORSO, LIMB, LIMB, TORSO, LIMB, LIMB,
+                                   HEAD, HEAD, HEAD, HEAD], np.int64)
+SILHOUETTE_SEGMENTS = np.concatenate([POSE_CONNECTIONS, [(8, 11)]])           # the 17 connections and the hip line
+SILHOUETTE_SEGMENT_CLASS = np.array([HEAD] * 5 + [TORSO, LIMB, LIMB, TORSO, LIMB, LIMB, TORSO, LIMB, LIMB, TORSO, LIMB, LIMB, TORSO], np.int64)
+SILHOUETTE_COORD_LIMIT = 1 << 14                        # what ta_poses_paint accepts
+POSE_COLORMAP = build_colormap()                        # module-global and stateful like FACE_COLORMAP: a track keeps its colour over calls
+
+
+def _one_device(device, who):
+    if isinstance(device, (list, tuple)):
+        raise ValueError('`device`: %s does not offer fan-out over a device list yet; pass one device' % who)
+
+
+def _permilles(head, torso, limb, min_radius):
+    p = [int(round(float(v) * 1000)) for v in (head, torso, limb)]
+    if not all(0 <= v <= 1000 for v in p):
+        raise ValueError('head, torso and limb must be within 0 .. 1, got %r' % ((head, torso, limb),))
+    if isinstance(min_radius, bool) or not isinstance(min_radius, (int, np.integer)) or not 0 <= min_radius <= 4096:
+        raise ValueError('min_radius must be an int within 0 .. 4096, got %r' % (min_radius,))
+    return p, int(min_radius)
+
+
+def pack_silhouettes(poses_per_frame, colors=None, alpha=255):
+    """-> (pose_counts (n_frames,) int32, keypoints (P, 18, 3) int32, rgba (P, 4) uint8), what `Context.poses_paint` takes:
+    the skeletons frame by frame in list order, coordinates truncated as pack_poses truncates them, an absent joint as
+    (0, 0, 0).  `colors`: None (white), one (r, g, b), one per pose ((P, 3)), or 'track': POSE_COLORMAP (a build_colormap()) of
+    pose['pose_track'], else of pose['track'], else of the pose's index in its frame -- the same id gets the same colour in
+    every frame and every later call.  `alpha`: 0 .. 255, one for all or one per pose.  Host only, no device."""
+    per_frame = [_as_list(poses) for poses in poses_per_frame]
+    k, _ = _keypoints(per_frame)
+    present = k[..., 2] != 0
+    xy = np.where(present[..., None], k[..., :2], 0.0)
+    if not np.all(np.abs(xy) < SILHOUETTE_COORD_LIMIT):
+        raise ValueError('keypoint coordinates must be finite and below 2^14 in size')
+    kp = np.concatenate([np.trunc(xy).astype(np.int32), present[..., None].astype(np.int32)], -1)
+    counts = np.array([len(poses) for poses in per_frame], np.int32)
+    n = len(kp)
+    rgba = np.empty((n, 4), np.uint8)
+    if colors is None:
+        rgba[:, :3] = 255
+    elif isinstance(colors, str):
+        if colors != 'track':
+            raise ValueError("colors must be None, one (r, g, b), one per pose or 'track', got %r" % (colors,))
+        at = 0
+        for poses in per_frame:
+            for i, pose in enumerate(poses):
+                key = pose.get('pose_track')
+                if key is None:
+                    key = pose.get('track')
+                rgba[at, :3] = POSE_COLORMAP(i if key is None else key)
+                at += 1
+    else:
+        c = np.asarray(colors)
+        if c.shape not in ((3,), (n, 3)) or c.dtype.kind not in 'iu' or c.size and (c.min() < 0 or c.max() > 255):
+            raise ValueError("colors must be None, one (r, g, b), one per pose or 'track', got %r" % (colors,))
+        rgba[:, :3] = c
+    a = np.asarray(alpha)
+    if a.shape not in ((), (n,)) or a.dtype.kind not in 'iu' or a.size and (a.min() < 0 or a.max() > 255):
+        raise ValueError('alpha must be an int 0 .. 255, one for all or one per pose, got %r' % (alpha,))
+    rgba[:, 3] = a
+    return counts, kp, rgba
+
+
+def pose_boxes(poses_per_frame, shapes, head=0.09, torso=0.09, limb=0.05, min_radius=2):
+    """[(frame, pose, x0, y0, x1, y1)]: for every skeleton with a present joint the extent of its present joints widened by
+    its largest radius (max(min_radius, size x share) per class, ta_poses_paint's) and clipped to its frame, as the
+    half-open box [x0, x1) x [y0, y1) -- everything its silhouette can cover; empty ones left out.  `shapes`: pack_blur's.
+    Host only."""
+    permille, min_radius = _permilles(head, torso, limb, min_radius)
+    counts, kp, _ = pack_silhouettes(poses_per_frame)
+    sizes = _frame_sizes(shapes, len(counts))
+    out, at = [], 0
+    for f, n in enumerate(counts):
+        h, w = int(sizes[f][0]), int(sizes[f][1])
+        for i in range(int(n)):
+            q = kp[at + i].astype(np.int64)
+            at_joint = q[q[:, 2] != 0]
+            if not len(at_joint):
+                continue
+            lo, hi = at_joint[:, :2].min(0), at_joint[:, :2].max(0)
+            m = int((hi - lo).max())
+            r = max(max(min_radius, m * p // 1000) for p in permille)
+            x0, y0, x1, y1 = max(int(lo[0]) - r, 0), max(int(lo[1]) - r, 0), min(int(hi[0]) + r + 1, w), min(int(hi[1]) + r + 1, h)
+            if x1 > x0 and y1 > y0:
+                out.append((f, i, x0, y0, x1, y1))
+        at += int(n)
+    return out
+
+
+def _per_batch(batches, poses_per_frame, who):
+    """The result lists of each batch of a list of batches (frames counted through, as the tone callers count them)."""
+    total = sum(b.shape[0] for b in batches)
+    per_frame = list(poses_per_frame)
+    if len(per_frame) > total:
+        raise ValueError('%s: %d result lists for %d frames' % (who, len(per_frame), total))
+    out, at = [], 0
+    for b in batches:
+        out.append(per_frame[at:at + b.shape[0]])
+        at += b.shape[0]
+    return out
+
+
+def pose_masks(frames_or_shape, poses_per_frame, head=0.09, torso=0.09, limb=0.05, min_radius=2, ctx=None, device=None):
+    """Mattes of the people: a NEW resident batch (a list of them for a list of batches) of the frames' size with 255 in all
+    three bands where a skeleton's silhouette is and 0 elsewhere -- one allocation and one ta_poses_paint with clear=1.
+    `image.composite_frames` and `image.paste_frames` take it as `mask`.  `frames_or_shape`: a lib.Frames batch, a list of
+    them, or a shape (N, H, W[, 3]) (then `ctx`, or the context of `device`, owns the result).
+
+    A silhouette is a disc at every present joint and a capsule along every connection (the 17 of POSE_CONNECTIONS and the
+    hip line), of radius max(min_radius, share x size) with size the larger side of the present joints' extent.  The
+    default shares come from geometry, not from tuning on data: a standing person is about eight heads tall, so a head's
+    radius is about size / 16 and 0.09 x size covers it from the nose or an ear; the hip joints lie about size / 6 apart,
+    so 0.09 x size closes the torso between the two neck-hip capsules; a thigh is about 0.05 x size in half-width."""
+    who = 'pose_masks'
+    _one_device(device, who)
+    permille, min_radius = _permilles(head, torso, limb, min_radius)
+    if isinstance(frames_or_shape, lib.Frames) or (isinstance(frames_or_shape, (list, tuple)) and frames_or_shape
+                                                   and isinstance(frames_or_shape[0], lib.Frames)):
+        batches, listed = image._batches(frames_or_shape, who)
+        plans = [(ctx if ctx is not None else b.ctx, b.shape[:3]) for b in batches]
+    else:
+        try:
+            n, h, w = (int(v) for v in tuple(frames_or_shape)[:3])
+        except (TypeError, ValueError):
+            raise ValueError('%s: a lib.Frames batch, a list of them or a shape (N, H, W[, 3]), got %r' % (who, frames_or_shape)) from None
+        if ctx is None:
+            from . import runtime
+            ctx = runtime.get_context(device)
+        plans, listed = [(ctx, (n, h, w))], False
+    total = sum(s[0] for _, s in plans)
+    per_frame = list(poses_per_frame)
+    if len(per_frame) > total:
+        raise ValueError('%s: %d result lists for %d frames' % (who, len(per_frame), total))
+    packed, at = [], 0
+    for _, (n, h, w) in plans:                              # everything is packed and checked before anything is allocated
+        mine = per_frame[at:at + n]
+        packed.append(pack_silhouettes(mine + [[]] * (n - len(mine))))
+        at += n
+    outs = []
+    for (c, (n, h, w)), (counts, kp, rgba) in zip(plans, packed):
+        out = lib.Frames.zeros(c, n, h, w)
+        if n:
+            c.poses_paint(out, counts, kp, rgba, permille, min_radius, clear=True)
+        outs.append(out)
+    return outs if listed else outs[0]
+
+
+def paint_poses(frames, poses_per_frame, colors='track', alpha=128, head=0.09, torso=0.09, limb=0.05, min_radius=2, ctx=None,
+                device=None):
+    """Paint every skeleton's silhouette into the resident batch `frames` (a lib.Frames, or a list of them) in place, one
+    list of poses per frame: translucent people, by default coloured by track (pose['pose_track'] as `PoseTracker` writes
+    it; pack_silhouettes' `colors` and `alpha`).  A pixel is blended once per person that covers it, however many of that
+    person's limbs do; people of one frame in list order.  The shape: pose_masks'."""
+    who = 'paint_poses'
+    _one_device(device, who)
+    permille, min_radius = _permilles(head, torso, limb, min_radius)
+    batches, _ = image._batches(frames, who)
+    per_batch = _per_batch(batches, poses_per_frame, who)
+    if not isinstance(colors, str) and colors is not None and np.ndim(colors) == 2:
+        colors, at, each = np.asarray(colors), 0, []       # one per pose: cut as the poses are
+        for mine in per_batch:
+            n = sum(len(_as_list(p)) for p in mine)
+            each.append(colors[at:at + n])
+            at += n
+        packed = [pack_silhouettes(mine, c, alpha) for mine, c in zip(per_batch, each)]
+    else:
+        packed = [pack_silhouettes(mine, colors, alpha) for mine in per_batch]
+    for b, (counts, kp, rgba) in zip(batches, packed):
+        if len(kp):
+            (ctx if ctx is not None else b.ctx).poses_paint(b, counts, kp, rgba, permille, min_radius)
+    return frames
+
+
+def pack_pose_blur(poses_per_frame, shapes, radius=None, method='gaussian', block=None, head=0.09, torso=0.09, limb=0.05,
+                   min_radius=2):
+    """-> (regions, pixelate?) for blur_poses: pose_boxes' boxes as lib.BLUR_DT records (`radius`: GaussianBlur's, None:
+    max(w, h) / 8 of the box, blur_faces' rule) or lib.PIXELATE_DT records (`block`: None: max(1, max(w, h) // 8)), shape
+    'box'.  Every argument is checked here.  Host only."""
+    if method not in BLUR_METHODS:
+        raise ValueError("method must be 'gaussian' or 'pixelate', got %r" % (method,))
+    pixelate = method == 'pixelate'
+    if pixelate:
+        if radius is not None:
+            raise ValueError("radius belongs to method='gaussian'; method='pixelate' takes block")
+        if block is not None and (isinstance(block, bool) or not isinstance(block, (int, np.integer))
+                                  or not 1 <= block <= lib.RESAMPLE_SIDE_LIMIT):
+            raise ValueError('block must be an int within 1 .. %d, got %r' % (lib.RESAMPLE_SIDE_LIMIT, block))
+    else:
+        if block is not None:
+            raise ValueError("block belongs to method='pixelate'; method='gaussian' takes radius")
+        if radius is not None and not 0 <= float(radius) <= BLUR_RADIUS_LIMIT:
+            raise ValueError('radius must be within 0 .. %g, got %r' % (BLUR_RADIUS_LIMIT, radius))
+    rows = []
+    for f, _, x0, y0, x1, y1 in pose_boxes(poses_per_frame, shapes, head, torso, limb, min_radius):
+        if pixelate:
+            v = max(1, max(x1 - x0, y1 - y0) // 8) if block is None else int(block)
+            rows.append((f, x0, y0, x1, y1, lib.BLUR_BOX, min(v, lib.RESAMPLE_SIDE_LIMIT)))
+        else:
+            v = max(x1 - x0, y1 - y0) / 8 if radius is None else float(radius)
+            rows.append((f, x0, y0, x1, y1, lib.BLUR_BOX, min(v, BLUR_RADIUS_LIMIT)))
+    return np.array(rows, lib.PIXELATE_DT if pixelate else lib.BLUR_DT), pixelate
+
+
+def _free(batches):
+    for b in batches:
+        b.free()
+
+
+def blur_poses(frames, poses_per_frame, radius=None, method='gaussian', block=None, head=0.09, torso=0.09, limb=0.05,
+               min_radius=2, ctx=None, device=None):
+    """Make whole people unrecognisable in the resident batch `frames` (a lib.Frames, or a list of them) in place: clothes,
+    tattoos and build go with the face.  A copy of the frames (`image.copy_frames`) is blurred -- or with
+    method='pixelate' turned into a mosaic -- over every skeleton's box (pose_boxes; in list order, `radius` / `block` as
+    blur_faces takes them), and the copy is pasted back under the people's matte (`pose_masks`) in one whole-frame
+    `image.composite_frames`: outside the silhouettes no pixel changes.  The shape: pose_masks'."""
+    who = 'blur_poses'
+    _one_device(device, who)
+    batches, _ = image._batches(frames, who)
+    per_batch = _per_batch(batches, poses_per_frame, who)
+    plans = [pack_pose_blur(mine, b.shape, radius, method, block, head, torso, limb, min_radius) for b, mine in zip(batches, per_batch)]
+    for b, mine, (regions, pixelate) in zip(batches, per_batch, plans):
+        if not len(regions):
+            continue
+        c = ctx if ctx is not None else b.ctx
+        copy = image.copy_frames(b, ctx=c)
+        matte = None
+        try:
+            if pixelate:
+                copy.pixelate(regions, ctx=c)
+            else:
+                copy.blur(regions, ctx=c)
+            matte = pose_masks(b, mine, head, torso, limb, min_radius, ctx=c)
+            image.composite_frames(b, copy, matte, ctx=c)
+        finally:
+            _free([copy] + ([matte] if matte is not None else []))
+    return frames
+
+
+def spotlight_poses(frames, poses_per_frame, dim=0.4, head=0.09, torso=0.09, limb=0.05, min_radius=2, ctx=None, device=None):
+    """Darken everything but the people of the resident batch `frames` (a lib.Frames, or a list of them) in place:
+    `image.brightness_frames(frames, dim)`, then the original pixels pasted back under the people's matte (`pose_masks`)."""
+    who = 'spotlight_poses'
+    _one_device(device, who)
+    _permilles(head, torso, limb, min_radius)
+    lut = image.brightness_lut(dim)
+    batches, _ = image._batches(frames, who)
+    per_batch = _per_batch(batches, poses_per_frame, who)
+    for mine in per_batch:
+        pack_silhouettes(mine)                              # checked before anything is launched
+    for b, mine in zip(batches, per_batch):
+        c = ctx if ctx is not None else b.ctx
+        copy = image.copy_frames(b, ctx=c)
+        matte = None
+        try:
+            image.point_frames(b, lut, ctx=c)
+            matte = pose_masks(b, mine, head, torso, limb, min_radius, ctx=c)
+            image.composite_frames(b, copy, matte, ctx=c)
+        finally:
+            _free([copy] + ([matte] if matte is not None else []))
+    return frames
+
+
+def anonymize_poses(image, poses, radius=None, method='gaussian', block=None, head=0.09, torso=0.09, limb=0.05, min_radius=2,
+                    device=None):
+    """A copy of the host image (uint8 (H, W, 3)) with every person (dict or list of dicts, as pose_estimation returns them)
+    blurred: `blur_poses` of the uploaded image, as anonymize_faces is to blur_faces."""
+    from . import runtime
+    _one_device(device, 'anonymize_poses')
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3 or image.shape[2] != 3:
+        raise ValueError('expected a uint8 (H, W, 3) RGB image, got %s %s' % (image.dtype, image.shape))
+    pack_pose_blur([poses], image.shape[:2], radius, method, block, head, torso, limb, min_radius)
+    frames = runtime.get_context(device).upload(image[None])
+    try:
+        return blur_poses(frames, [poses], radius, method, block, head, torso, limb, min_radius).download()[0]
+    finally:
+        frames.free()
+
+
 def anonymize_faces(image, faces, radius=None, margin=0.0, shape='box', method='gaussian', block=None):
     """A copy of the host image (uint8 (H, W, 3)) with every face (dict or list of dicts, face_tracking's included)
     blurred: Pillow's crop / GaussianBlur(radius) / paste of each box, or with method='pixelate' its crop / resize(BOX) /
