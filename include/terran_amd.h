@@ -1016,6 +1016,47 @@ int ta_poses_track(ta_ctx* ctx, int n_sequences, const int32_t* frames_per_seque
 int ta_poses_paint(ta_ctx* ctx, ta_frames* frames, int n_frames, const int32_t* pose_counts, const int32_t* keypoints,
                    const uint8_t* rgba, int n_poses, const int32_t radius_permille[3], int min_radius, int clear);
 
+/* ---- where was this person in between?  tracked rows filled across missed frames and points ------------------------------ */
+/* Host arrays, frames concatenated as in ta_poses_track: counts (n_frames,) int32, the frames consecutive frames of ONE
+ * sequence; points (n_rows, n_points, 3) int32 (x, y, present): a point is present iff its third value is != 0, the x, y of
+ * an absent point are ignored; n_points 1 .. 18: 18 for skeletons, 7 for faces (the two corners of the box and the five
+ * landmarks); prev (n_rows,) int32, the global row of each row's predecessor or -1, exactly what ta_poses_track answers.  All
+ * arithmetic is integer, so the answer is defined bit for bit.  G = max_gap + 1.
+ *   frame(r)  the frame that row r lies in
+ *   link      a = prev[b], d = frame(b) - frame(a) >= 1 (checked); a chain is the rows joined by links, whatever their d; no
+ *             two rows have the same predecessor (checked), so a chain is a line and a row has at most one successor
+ *   rows      every input row is an output row of its frame, in input order, first.  A link with 2 <= d <= G adds one
+ *             SYNTHESIZED row to every frame t with frame(a) < t < frame(b); a link with d > G adds none.  The synthesized rows
+ *             of a frame follow its real rows, ordered by their link's b ascending (b is a global row: a strict order)
+ *   points    for output row R at frame t, of chain C, and point j: if R is a real row whose j is present, its x, y and third
+ *             value are copied unchanged.  Otherwise let r0 be the nearest real row of C in a frame before t whose j is
+ *             present, r1 the nearest one in a frame after t, t0 = frame(r0), t1 = frame(r1), (x0, y0) and (x1, y1) their j.
+ *             If both exist and t1 - t0 <= G, the point is present with the third value `mark`, and each of x, y is
+ *                 v = v0 + floor((2 * (v1 - v0) * (t - t0) + (t1 - t0)) / (2 * (t1 - t0)))      (floor division)
+ *             the linear interpolation rounded to nearest, halves towards +infinity.  Otherwise the point is (0, 0, 0): a
+ *             row in no chain, or one whose neighbours with that point are too far apart, keeps its absent points absent,
+ *             nothing is held past a chain's first or last observation of a point, and nothing is filled across a link
+ *             with d > G
+ *   range     every |x|, |y| of every point of a row, present or not, is below 2^22 (checked), so |v1 - v0| < 2^23, t - t0
+ *             <= 30 and t1 - t0 <= 31: the numerator is below 2^23 * 31 * 2 + 31 < 2^29 in size, exact in int32 (and in any
+ *             wider type); the device keeps int32
+ * Outputs: out_counts (n_frames,) int32, the rows of each output frame; out_points (n_out, n_points, 3) int32; out_source
+ * (n_out, 2) int32: (r, r) for the real row r, (a, b) for a synthesized row of the link a = prev[b]; *n_out = n_rows + the sum
+ * of d - 1 over the links that add rows, which a caller can compute from counts and prev alone.  The answer depends on nothing
+ * the device schedules: the rank of a synthesized row is a prefix count over the rows of the G frames behind its frame,
+ * walked in order by one workgroup, and every output word has one writer.  Scratch (the context's scratch block) is the
+ * input, the output and four words a row; nothing grows faster than rows x points.
+ * Checked on the host before any launch; outputs untouched on failure, except *n_out.  TA_E_OVERFLOW: more than 16384 input
+ * rows, or more than 16384 output rows, in one frame; more than 2^31 - 1 output rows in all (*n_out = INT32_MAX); out_capacity
+ * below the rows needed -- *n_out is then written with that number, so a caller may ask with capacity 0 (and NULL outputs).
+ * TA_E_INVALID: a negative count; counts that do not sum to n_rows; a NULL array that has rows; n_points outside 1 .. 18;
+ * max_gap outside 0 .. 30; mark outside 1 .. 255; any x, y of any point of a row at or above 2^22 in size; a prev that is
+ * neither -1 nor a row of an earlier frame; two rows with the same prev (a chain, not a tree).  n_frames == 0, empty frames and
+ * rows without links succeed.  n_out may be NULL. */
+int ta_tracks_fill(ta_ctx* ctx, int n_frames, const int32_t* counts, const int32_t* points, int n_points,
+                   const int32_t* prev, int n_rows, int max_gap, int mark, int32_t* out_counts, int32_t* out_points,
+                   int32_t* out_source, int out_capacity, int32_t* n_out);
+
 /* Workload statistics of the last ta_openpose_run / ta_openpose_group on this context: heat-map peaks found over
  * all images and parts (wrapper.py:235-262) and limb connections accepted by the greedy matching (wrapper.py:335-366). */
 int ta_openpose_last_stats(const ta_ctx* ctx, int64_t* peaks, int64_t* connections);

@@ -14,6 +14,7 @@ from .openpose import OpenPose, PoseOverflow                      # noqa: F401
 from .gallery import FaceGallery, cluster_faces                   # noqa: F401
 from .link import link_faces_poses, head_boxes                    # noqa: F401
 from .tracking import PoseTracker, PoseTracking, pose_tracking    # noqa: F401
+from .tracking import fill_pose_tracks, fill_face_tracks          # noqa: F401
 from .vis import pose_masks, paint_poses, blur_poses, spotlight_poses, anonymize_poses    # noqa: F401
 
 face_detection = Detection(lazy=True)

@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libterran_amd.so')
 SOURCES = ['runtime.hip', 'frames.hip', 'conv_split.hip', 'conv_split_modes.hip', 'conv_sym.hip', 'conv_dwpw.hip', 'conv_igemm.hip', 'layers.hip', 'model_load.hip', 'model_plan.hip', 'model_run.hip', 'retinaface_post.hip', 'arcface_post.hip', 'gallery.hip',
            'gallery_cluster.hip', 'openpose_post.hip', 'draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip', 'combine.hip', 'color.hip', 'yuv.hip', 'jpeg_host.hip', 'jpeg.hip',
-           'jpeg_encode.hip', 'tiles.hip', 'detections_merge.hip', 'poses_merge.hip', 'faces_poses_link.hip', 'poses_track.hip', 'poses_paint.hip']
+           'jpeg_encode.hip', 'tiles.hip', 'detections_merge.hip', 'poses_merge.hip', 'faces_poses_link.hip', 'poses_track.hip', 'poses_paint.hip', 'tracks_fill.hip']
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-Wall', '-Wno-unused-function']
 
 
@@ -70,7 +70,7 @@ def build(force=False, verbose=False):
         # color: convert()'s float32 matrix sums and the HSV conversions' float32 / double steps; gallery: l2norm_kernel's
         # normalisation, which arcface_post.hip compiles this way; detections_merge: the NMS expression of retinaface_post.hip;
         # tiles: no float at all, the flags are the same for the pair; poses_merge: one double multiply per threshold, never fused
-        # into what follows; faces_poses_link, poses_track and poses_paint hold no float and are not listed)
+        # into what follows; faces_poses_link, poses_track, poses_paint and tracks_fill hold no float and are not listed)
         exact = src.endswith('_post.hip') or src in ('draw.hip', 'blur.hip', 'resample.hip', 'transform.hip', 'tone.hip', 'filter.hip',
                                                      'combine.hip', 'color.hip', 'gallery.hip', 'gallery_cluster.hip', 'tiles.hip',
                                                      'detections_merge.hip', 'poses_merge.hip')

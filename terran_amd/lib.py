@@ -109,6 +109,8 @@ SIGNATURES = {
     'ta_poses_track': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                c_void_p, c_void_p]),
     'ta_poses_paint': (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int]),
+    'ta_tracks_fill': (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                               P(C.c_int32)]),
     'ta_arcface_embed_crops': (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     'ta_arcface_embed_faces': (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     'ta_arcface_embed_faces_multi': (c_int, [c_void_p, P(c_void_p), c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
@@ -231,6 +233,8 @@ assert POSE_GROUP_DT.itemsize == 40
 LINK_MAX_PER_FRAME = 16384
 # ta_poses_track: the skeletons it takes per frame
 TRACK_MAX_PER_FRAME = 4096
+# ta_tracks_fill: the rows it takes, and gives, per frame
+FILL_MAX_PER_FRAME = 16384
 
 # ta_color_region, ta_color_op (include/terran_amd.h) and the kinds TA_COLOR_*; shapes: BLUR_*
 COLOR_MATRIX, COLOR_RGB2YCBCR, COLOR_YCBCR2RGB, COLOR_RGB2HSV, COLOR_HSV2RGB, COLOR_LUT3D = range(6)
@@ -767,6 +771,36 @@ class Context:
         self.check(self.lib.ta_poses_paint(self.h, frames.h, n, ptr(pc) if n else None, ptr(keypoints) if npose else None,
                                            ptr(rgba) if npose else None, npose, ptr(permille), int(min_radius), int(bool(clear))))
         return frames
+
+    def tracks_fill(self, counts, points, prev, max_gap=5, mark=2):
+        """ta_tracks_fill: the tracked rows of consecutive frames (counts (n_frames,); points (R, n_points, 3) int32 (x, y, present);
+        prev (R,) int32 as poses_track answers it, frames concatenated) with a synthesized row in every frame a link of 2 ..
+        max_gap + 1 frames skips and every absent point interpolated between the chain's nearest rows that have it, at most max_gap
+        + 1 frames apart, third value `mark` -> (out_counts (n_frames,) int32, out_points (n_out, n_points, 3) int32, out_source
+        (n_out, 2) int32: (r, r) for a real row, (a, b) for a synthesized one)."""
+        counts = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+        points = np.ascontiguousarray(points, dtype=np.int32)
+        if points.ndim != 3 or points.shape[2] != 3:
+            raise ValueError('tracks_fill: points must be (rows, n_points, 3) int32, got %s' % (points.shape,))
+        prev = np.ascontiguousarray(prev, dtype=np.int32).reshape(-1)
+        if len(prev) != len(points):
+            raise ValueError('tracks_fill: %d prev entries for %d rows' % (len(prev), len(points)))
+        n, rows, npts = len(counts), len(points), points.shape[1]
+        # the rows the call will give: a link of d frames, 2 <= d <= max_gap + 1, adds d - 1.  Whatever is wrong with counts or
+        # prev the library reports; here such an entry just adds nothing
+        cap = rows
+        if rows and n and (counts >= 0).all() and int(counts.sum()) == rows:
+            frame = np.repeat(np.arange(n), counts)
+            linked = (prev >= 0) & (prev < rows)
+            d = frame[linked] - frame[prev[linked]]
+            cap += int((d[(d >= 2) & (d <= int(max_gap) + 1)] - 1).sum())
+        oc, op, src = np.zeros(max(n, 1), np.int32), np.empty((max(cap, 1), npts, 3), np.int32), np.empty((max(cap, 1), 2), np.int32)
+        n_out = C.c_int32(0)
+        self.check(self.lib.ta_tracks_fill(self.h, n, ptr(counts) if n else None, ptr(points) if rows else None, npts, ptr(prev) if rows else None,
+                                           rows, int(max_gap), int(mark), ptr(oc), ptr(op), ptr(src), cap, C.byref(n_out)))
+        if n_out.value != cap:
+            raise TerranAmdError(E_INVALID, 'tracks_fill: the library gave %d rows, counts and prev give %d' % (n_out.value, cap))
+        return oc[:n], op[:cap], src[:cap]
 
     def cosine_distance(self, a, b):
         a = np.ascontiguousarray(a, dtype=np.float32)

@@ -312,3 +312,111 @@ def pose_tracking(*, video=None, max_gap=None, estimator=None, **rule):
     elif not isinstance(estimator, (facade.Estimation, facade.TiledEstimation)):
         raise ValueError('`estimator` must be an instance of `Estimation` or `TiledEstimation`.')
     return PoseTracking(estimator=estimator, tracker=PoseTracker(max_gap=max_gap, **rule))
+
+
+# ---- tracks filled across missed frames and joints ----------------------------------------------------------------------------
+# Not the reference's (its tracker "will not interpolate a face whenever there's a missing observation in between"): the rule of
+# ta_tracks_fill (include/terran_amd.h), in integers and on the device; the host builds the links from the ids and the dicts
+# from the answer.
+def prev_of_ids(ids_per_frame):
+    """Per frame a sequence of track ids -> prev (rows,) int32: for every row, frames concatenated, the global row that carried
+    its id last, in whichever earlier frame, or -1.  An id that is None or negative joins no chain; the same id twice in one
+    frame is a ValueError."""
+    last, prev = {}, []
+    for t, ids in enumerate(ids_per_frame):
+        seen = set()
+        for k in ids:
+            k = None if k is None else int(k)
+            if k is None or k < 0:
+                prev.append(-1)
+                continue
+            if k in seen:
+                raise ValueError('frame %d carries id %d twice: a track has one row a frame' % (t, k))
+            seen.add(k)
+            prev.append(last.get(k, -1))
+            last[k] = len(prev) - 1                 # the row just appended
+    return np.array(prev, np.int32).reshape(-1)
+
+
+def _own(d):
+    """A shallow copy of a result dict with its own arrays."""
+    return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in d.items()}
+
+
+def _fill_tracks(who, per_frame, pack, n_points, unpack, max_gap, mark, key, carry, ctx, device):
+    if isinstance(device, (list, tuple)):
+        raise ValueError('`device`: %s does not offer fan-out over a device list yet; pass one device' % who)
+    frames = [list(v) for v in per_frame]
+    if any(not isinstance(d, dict) for v in frames for d in v):
+        raise ValueError('%s takes one list of dicts per frame' % who)
+    prev = prev_of_ids([[d.get(key) for d in v] for v in frames])
+    rows = [d for v in frames for d in v]
+    points = np.array([pack(d) for d in rows], np.int32).reshape(-1, n_points, 3)
+    counts = np.array([len(v) for v in frames], np.int32)
+    if ctx is None:
+        from . import runtime
+        ctx = runtime.get_context(device)
+    out_counts, out_points, out_source = ctx.tracks_fill(counts, points, prev, int(max_gap), int(mark))
+    out, at = [], 0
+    for c in out_counts.tolist():
+        mine = []
+        for (a, b), p in zip(out_source[at:at + c].tolist(), out_points[at:at + c]):
+            if a == b:
+                d = _own(rows[a])
+                unpack(d, p, True)
+            else:
+                d = {'filled': True, key: rows[b][key]}
+                unpack(d, p, False)
+                scores = [rows[r]['score'] for r in (a, b) if 'score' in rows[r]]
+                if scores:
+                    d['score'] = min(scores)
+                for k in carry:
+                    if k in rows[a]:
+                        d[k] = rows[a][k]
+            mine.append(d)
+        out.append(mine)
+        at += c
+    return out
+
+
+def fill_pose_tracks(poses_per_frame, max_gap=5, mark=2, key='pose_track', carry=('text', 'track', 'cluster'), ctx=None, device=None):
+    """The skeletons of one clip, one list of dicts per consecutive frame with the track ids `PoseTracker` wrote under `key`, ->
+    new per-frame lists in which a track that missed up to `max_gap` frames has a synthesized skeleton in each of them, behind
+    the frame's own skeletons, and a joint that a track lost for up to `max_gap` frames is interpolated between the nearest
+    frames that have it (ta_tracks_fill states the rule to the bit).  A filled joint carries `mark` as its third value, which
+    `vis`, `link`, `paint` and the tracker take as present.  A synthesized dict carries 'filled': True, the id under `key`,
+    the smaller 'score' of its two neighbours and the `carry` keys of its predecessor.  The input and its arrays are not
+    modified: every returned dict is a shallow copy with its own arrays.  An id that is missing, None or negative joins no chain."""
+    def pack(d):
+        return np.asarray(d['keypoints']).reshape(18, 3)
+
+    def unpack(d, p, real):
+        d['keypoints'] = p.copy()
+
+    return _fill_tracks('fill_pose_tracks', poses_per_frame, pack, 18, unpack, max_gap, mark, key, carry, ctx, device)
+
+
+def pack_face(face):
+    """A face dict -> its 7 points (7, 3) int32, all present: the two corners of 'bbox', then the five 'landmarks'; fractions
+    are cut off as blur_faces cuts them."""
+    p = np.ones((7, 3), np.int32)
+    p[:2, :2] = np.asarray(face['bbox']).reshape(2, 2).astype(np.int32)
+    p[2:, :2] = np.asarray(face['landmarks']).reshape(5, 2).astype(np.int32)
+    return p
+
+
+def unpack_face(points):
+    """(7, 3) points -> ('bbox' int32 (4,), 'landmarks' int32 (5, 2))."""
+    points = np.asarray(points, np.int32).reshape(7, 3)
+    return points[:2, :2].reshape(4).copy(), points[2:, :2].copy()
+
+
+def fill_face_tracks(faces_per_frame, max_gap=5, key='track', carry=('text', 'cluster', 'pose'), ctx=None, device=None):
+    """`fill_pose_tracks` for faces with the ids `face_tracking` wrote under `key`: a face is its box's two corners and its five
+    landmarks, 7 points that are all present, so only whole missed frames are filled; a synthesized face carries 'bbox' int32
+    (4,) and 'landmarks' int32 (5, 2).  The faces a frame had are returned as they were."""
+    def unpack(d, p, real):
+        if not real:
+            d['bbox'], d['landmarks'] = unpack_face(p)
+
+    return _fill_tracks('fill_face_tracks', faces_per_frame, pack_face, 7, unpack, max_gap, 1, key, carry, ctx, device)
